@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the eray ray-tracing hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: set-up, W warmup steps, the K timed
+steps, the outputs of the last step (--dump-outputs) and the result line.  --full adds every other
+leg to the line: the frame kernel's dispatch-timed figures and roofline, fill floors and write
+ceilings, the beyond-the-cache ring, the moving-camera, anti-aliasing, one-shot and material-update
+lines, the north_star sub-record and the CPU baseline (--no-cpu-baseline, --no-moving-camera and
+--no-north-star drop legs of a --full run).
 
 Metric (BASELINE.json): Mrays/s + frame ms at 1920x1080 cube.obj, 1/2/4/8-GPU tile scaling.
 Workload (configs[1]): objects/cube.obj with src/main.rs's scene and material
@@ -397,6 +404,24 @@ def north_star_line(device: int, steps: int, slot_counts=None) -> dict:
             "variants": variants}
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: all files together (float32), under 64 MB
+DUMP_SEED = 20190523
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: each device tensor as directory/<name>.npy in float32 (f32 images as they
+    are, PPM bytes as their values).  A tensor over its share of DUMP_BYTES is written as a fixed
+    sample of its flattened elements: the indices come from DUMP_SEED and the element count alone,
+    so two builds run with the same arguments write the same elements."""
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            idx = np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=cap, dtype=np.int64)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def mesh_label(path: str) -> str:
     """The mesh as the JSON line names it: repo-relative when it is in the tree, else the file name
     (meshes generated on the box by eray_amd.meshgen)."""
@@ -517,6 +542,12 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline figure (kernel figures and roofline, fill floors, moving "
+                         "camera, AA, one-shot, material update, north_star, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (f32 images and PPM bytes, for N > 1 also the frames "
+                         "assembled on rank 0) as DIR/<name>.npy, float32, under 64 MB in all")
     ap.add_argument("--mesh", default=os.path.join(ROOT, "objects", "cube.obj"))
     ap.add_argument("--width", type=int, default=WIDTH,
                     help="frame width (strong) or width per GPU (weak); C2: 1920")
@@ -571,8 +602,9 @@ def main() -> None:
         dist.all_reduce(t, op=op)
         return t.item()
 
-    # main.rs's one-shot use, before anything else touches the GPU (N = 1 only)
-    oneshot = one_shot(args.mesh, args.width, args.height) if world == 1 and not args.no_moving_camera else None
+    # main.rs's one-shot use, before anything else touches the GPU (--full, N = 1 only)
+    oneshot = (one_shot(args.mesh, args.width, args.height)
+               if args.full and world == 1 and not args.no_moving_camera else None)
     mesh = load_obj_file(args.mesh)
     ctx = capi.Context(device)
     stream = torch.cuda.Stream()  # the render stream: shared by the library and torch
@@ -584,7 +616,7 @@ def main() -> None:
     scene = MainScene(ctx, *mesh, width, H, texture=TEXTURE, fov=frame_camera_fov(width, H))
     torch.cuda.synchronize()
     t_mat = time.perf_counter() - t_mat0
-    material_line = material_roofline(scene, stream) if rank == 0 else None
+    material_line = material_roofline(scene, stream) if args.full and rank == 0 else None
 
     # this rank's rows: interleaved 4-row bands r, r + N, ... (every rank an equal share of the scene
     # wherever it sits) or, --split blocks, the r-th block of PPM file rows
@@ -619,9 +651,9 @@ def main() -> None:
                     out_ppm=ppm[half * G].data_ptr(), ring=capi.frame_ring(n, alloc_rows, width, min(F, n)),
                     **band_args)
 
-    # one untimed instrumented frame: hit pixels and hit faces for the algorithmic-bytes model;
-    # being the first render of the camera it also builds the per-camera data (culling records,
-    # pixel rectangles, screen bins of large meshes): reported as scene_setup_ms
+    # one untimed instrumented frame: being the first render of the camera it builds the per-camera
+    # data (culling records, pixel rectangles, screen bins of large meshes), reported as
+    # scene_setup_ms; --full counts its hit pixels and hit faces for the algorithmic-bytes model
     face = torch.full((alloc_rows, width), -1, dtype=torch.int32, device="cuda")
     one_rgb = torch.empty((alloc_rows, width, 3), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
@@ -630,8 +662,10 @@ def main() -> None:
                **band_args)
     torch.cuda.synchronize()
     t_setup = time.perf_counter() - t_setup0
-    hit = face[:rows][face[:rows] >= 0]
-    hits, hit_faces = int(hit.numel()), int(torch.unique(hit).numel())
+    hits = hit_faces = 0
+    if args.full:
+        hit = face[:rows][face[:rows] >= 0]
+        hits, hit_faces = int(hit.numel()), int(torch.unique(hit).numel())
     del face, one_rgb
 
     gather = None
@@ -708,9 +742,82 @@ def main() -> None:
         elapsed = time.perf_counter() - t0
     if world > 1:
         elapsed = float(allreduce(elapsed, torch.float64, dist.ReduceOp.MAX))
-        hits_all = int(allreduce(hits, torch.int64, dist.ReduceOp.SUM))
-    else:
-        hits_all = hits
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: its frames' f32 images and PPM bytes in frame order (frame k
+        # is in slot k % slots); N > 1: rank 0's rows of the last batch and the frames it assembled
+        if world == 1:
+            last = [k % slots for k in range(n_timed - min(fps, slots), n_timed)]
+            whole = last == list(range(slots))
+            outputs = {"rgb": rgb if whole else rgb[last], "ppm": ppm if whole else ppm[last]}
+        else:
+            n_last = n_timed % G or G
+            first = ((n_timed - 1) // G % 2) * G
+            outputs = {"rgb": rgb[first:first + n_last], "ppm": ppm[first:first + n_last]}
+            if frames_out is not None:
+                outputs["frames"] = frames_out[:frames_assembled(n_last, world, rank, rotate)]
+        dump_outputs(args.dump_outputs, outputs)
+
+    def close():
+        if world > 1 and not rehearsal:
+            torch.cuda.synchronize()
+            rccl.close()
+        scene.close()
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    ms_per_step = elapsed / args.steps * 1e3
+    frame_ms = elapsed / n_timed * 1e3
+    is_c2 = (width, H) == (WIDTH, HEIGHT) and args.mesh.endswith("objects/cube.obj") and not args.brute_force
+    headline = {
+        "metric": "Mrays/s",
+        "value": round(width * H * n_timed / elapsed / 1e6, 3),
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 6),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": (f"synthetic scene of src/main.rs around {mesh_label(args.mesh)}"
+                 + (" (the reference's own file)" if args.mesh.endswith("objects/cube.obj") else "")
+                 + ", procedural material graph"),
+        "config": {
+            "workload": f"{'C2: ' if is_c2 else ''}{os.path.basename(args.mesh)}, {width}x{H} frame, "
+                        f"{width}x{rows} rows on rank 0, main.rs scene + material graph; step = {fps} frames, each: camera "
+                        "rays, first-hit scan, shading + shadow rays, f32 image and PPM bytes"
+                        + ((", assembled on rank k % N" if rotate else ", assembled on rank 0")
+                           + ": scene-camera gather over RCCL point-to-point" if world > 1 else "")
+                        + f"; {F} frames in flight per launch",
+            "mesh": mesh_label(args.mesh),
+            "triangles": int(len(mesh[0])),
+            "frame": [width, H],
+            "rows_per_gpu": rows,
+            "texture": TEXTURE,
+            "parallelism": (f"row tiles x{world} ({'interleaved 4-row bands' if bands else 'contiguous blocks'})"
+                            if world > 1 else "single GPU"),
+            "frames_per_step": fps,
+            "frames_per_launch": F,
+            "ring_slots": slots,
+            "camera": "static (value); see moving_camera",
+            **({"note": "weak scaling widens the frame to (1920 N) x 1080: not a BASELINE.json config"}
+               if world > 1 and args.scaling == "weak" else {}),
+            "culling": not args.brute_force,
+        },
+        "frame_ms": round(frame_ms, 6),
+        "material_graph_s": round(t_mat, 4),
+        "scene_setup_ms": round(t_setup * 1e3, 3),
+        **({"rehearsal": "all ranks on GPU 0, gloo collectives: not a measurement"} if rehearsal else {}),
+    }
+    if not args.full:  # a plain run ends here: every other leg is --full's
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        close()
+        return
+
+    hits_all = int(allreduce(hits, torch.int64, dist.ReduceOp.SUM)) if world > 1 else hits
     # the frame kernel's duration on this rank: launches of the line's size, each timed by its
     # dispatch's own start / end timestamps (eray_time_frames_ring); the same frames graph-replayed
     # between two events (launch gaps included); the latency of one frame alone per launch
@@ -794,59 +901,16 @@ def main() -> None:
         # the workload a committed counter summary (profiles/rNN/pmc_traffic*.json) must match
         pmc_key = {"mesh": mesh_label(args.mesh), "frame": [width, H], "rows_per_gpu": rows, "n_gpus": world,
                    "brute_force": bool(args.brute_force), "frames_per_launch": F}
-        is_c2 = (width, H) == (WIDTH, HEIGHT) and args.mesh.endswith("objects/cube.obj") and not args.brute_force
         pixels = width * rows
-        ms_per_step = elapsed / args.steps * 1e3
-        frame_ms = elapsed / n_timed * 1e3
-        rays = width * H * n_timed
-        value = rays / elapsed / 1e6
         alg = algorithmic_bytes(pixels, hits, hit_faces)
         gbs = alg / (kernel_ms * 1e-3) / 1e9
         launch_ms = kernel_ms * F
         result = {
-            "metric": "Mrays/s",
-            "value": round(value, 3),
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 6),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": (f"synthetic scene of src/main.rs around {mesh_label(args.mesh)}"
-                     + (" (the reference's own file)" if args.mesh.endswith("objects/cube.obj") else "")
-                     + ", procedural material graph"),
-            "config": {
-                "workload": f"{'C2: ' if is_c2 else ''}{os.path.basename(args.mesh)}, {width}x{H} frame, "
-                            f"{width}x{rows} rows on rank 0, main.rs scene + material graph; step = {fps} frames, each: camera "
-                            "rays, first-hit scan, shading + shadow rays, f32 image and PPM bytes"
-                            + ((", assembled on rank k % N" if rotate else ", assembled on rank 0")
-                               + ": scene-camera gather over RCCL point-to-point" if world > 1 else "")
-                            + f"; {F} frames in flight per launch",
-                "mesh": mesh_label(args.mesh),
-                "triangles": int(len(mesh[0])),
-                "frame": [width, H],
-                "rows_per_gpu": rows,
-                "texture": TEXTURE,
-                "parallelism": (f"row tiles x{world} ({'interleaved 4-row bands' if bands else 'contiguous blocks'})"
-                                if world > 1 else "single GPU"),
-                "frames_per_step": fps,
-                "frames_per_launch": F,
-                "ring_slots": slots,
-                "camera": "static (value); see moving_camera",
-                **({"note": "weak scaling widens the frame to (1920 N) x 1080: not a BASELINE.json config"}
-                   if world > 1 and args.scaling == "weak" else {}),
-                "culling": not args.brute_force,
-            },
-            "frame_ms": round(frame_ms, 6),
+            **headline,
             "render_kernel_ms": round(kernel_ms, 6),
             "frame_latency_ms": None if latency is None else round(latency["frame_kernel_ms"], 6),
             "graph_replay_ms_per_frame": round(replay_ms, 6),
-            "material_graph_s": round(t_mat, 4),
             "material_update": material_line,
-            "scene_setup_ms": round(t_setup * 1e3, 3),
             "gather": ({"kind": f"{args.gather}, every frame, batches of {G} overlapped with rendering, "
                                 + ("frame k on rank k % N" if rotate else "every frame on rank 0"),
                         "ms_per_frame_alone": round(gather_ms, 5)} if world > 1 else None),
@@ -854,7 +918,6 @@ def main() -> None:
             "moving_camera": moving,
             "one_shot": oneshot,
             "anti_aliased": aa_line,
-            **({"rehearsal": "all ranks on GPU 0, gloo collectives: not a measurement"} if rehearsal else {}),
             "hit_pixels": hits_all,
             "roofline": {
                 "bound": "hbm",
@@ -889,13 +952,7 @@ def main() -> None:
             result["cpu_baseline"] = cpu_baseline(mesh, width, H, frame_camera_fov(width, H), args.cpu_seconds)
         print(json.dumps(result), flush=True)
 
-    if world > 1 and not rehearsal:
-        torch.cuda.synchronize()
-        rccl.close()
-    scene.close()
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

@@ -11,6 +11,7 @@ for rep in 1 2; do
 for t in ${AB_TREES:-head}; do
   if [ $t = head ]; then D=.; else D=ab_$t; fi
   X=""; grep -q no-moving-camera $D/bench.py && X="--no-moving-camera"
+  grep -q -- '"--full"' $D/bench.py && X="$X --full"  # (render_kernel_ms is a --full figure since that option exists)
   (cd $D && timeout -k 10 300 python bench.py $(eval echo $AB_ARGS) --no-cpu-baseline $X > $GRAFT_REPO_ROOT/gpurun_out/ab_cfg_${t}_$rep.log 2>&1) || exit 1
   python - "$t" "$rep" <<'PY'
 import json,sys

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 D=${PMC_DIR:-pmc}  # output directory under gpurun_out/
 mkdir -p gpurun_out/$D
 export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:---steps 50 --warmup 5 --no-cpu-baseline --no-moving-camera}
+ARGS=${BENCH_ARGS:---full --steps 50 --warmup 5 --no-cpu-baseline --no-moving-camera}
 pass() {  # name counters...
   local name=$1; shift
   echo "=== pmc $name: $*"

@@ -9,10 +9,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu tests > $OUT/tests.log 2>&1
 rc=$?; tail -3 $OUT/tests.log; [ $rc -eq 0 ] || { grep -B5 -A40 "FAIL\|Error" $OUT/tests.log | head -150; exit $rc; }
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; [ $rc -eq 0 ] || { tail -c 3000 $OUT/bench.err; exit $rc; }
 cat $OUT/bench.json | cut -c1-600
-timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err
+timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err
 rc=$?; [ $rc -eq 0 ] || { tail -c 3000 $OUT/bench_prof.err; exit $rc; }
 [ "${NO_PMC:-0}" = 1 ] && exit 0
 pass() {  # dir name bench-args counters...
@@ -23,7 +23,7 @@ pass() {  # dir name bench-args counters...
   echo "pmc $d/$name rc=$rc"
   [ $rc -eq 0 ] || { tail -20 $OUT/$d/$name.log; exit $rc; }
 }
-C2ARGS="--steps 25 --warmup 3 --no-cpu-baseline --no-moving-camera --no-north-star"
+C2ARGS="--full --steps 25 --warmup 3 --no-cpu-baseline --no-moving-camera --no-north-star"
 for d in c2:"$C2ARGS" ns1:"--north-star-only --ns-slots 1 --steps 20" ns4:"--north-star-only --ns-slots 4 --steps 20"; do
   name=${d%%:*}; args=${d#*:}
   pass pmc_$name sq "$args" SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU

@@ -227,7 +227,7 @@ static void cpu_tests(const std::string& root) {
         CHECK(b.faces.size() == 12);
     });
     test("object::load_obj errors", [&] {
-        const std::string p = "/tmp/eray_host_test.obj";
+        const std::string p = "eray_host_test.obj";  // in the working directory (the tests run in a fresh one)
         auto write = [&](const char* text) {
             FILE* f = std::fopen(p.c_str(), "wb");
             std::fputs(text, f);
@@ -312,7 +312,7 @@ static void gpu_tests(const std::string& root, const std::string& ppm) {
 
 int main(int argc, char** argv) {
     bool gpu = false;
-    std::string root = ".", ppm = "/tmp/eray_host_c1.ppm";
+    std::string root = ".", ppm = "eray_host_c1.ppm";
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--gpu")) gpu = true;
         else if (!std::strcmp(argv[i], "--root") && i + 1 < argc) root = argv[++i];
