@@ -19,13 +19,14 @@
 
 #include "../../include/eray_hip.h"
 #include "internal.hpp"
+#include "owners.hpp"
 
 using namespace eray::gpu;
 
 namespace {
 thread_local std::string g_thread_error;
 constexpr size_t kMaxTags = 512;
-constexpr uint32_t kUnionRing = 4;
+constexpr uint32_t kUnionRing = 4;  // camera paths whose rectangle unions the host keeps
 
 struct HostObject {
     std::vector<float> raw;  // T*9 positions | T*9 normals | T*6 uvs
@@ -77,8 +78,8 @@ uint32_t texel_emit(const std::vector<eray_texel_node>& nodes, uint32_t idx, uin
 
 struct eray_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    Stream own_stream;
+    hipStream_t stream = nullptr;  // own_stream, or the caller's (eray_set_stream)
     std::string err;
 
     eray_camera camera{{0.0f, 0.0f, 0.0f}, {60.0f, 60.0f}, 1024u, 1.0f};  // Camera::default()
@@ -87,51 +88,40 @@ struct eray_ctx {
 
     bool geom_dirty = true, desc_dirty = true;
     uint64_t scene_gen = 0;  // bumped whenever geometry or descriptors are uploaded
-    TriHot* d_hot = nullptr;
-    TriShade* d_shade = nullptr;
-    TriCull* d_cull = nullptr;
-    TriCull* d_tcull = nullptr;  // kTraceSkipTris records: trace.hip's background skip
-    size_t tri_cap = 0;
-    float* d_raw = nullptr;
-    size_t raw_cap = 0;
-    ObjectDesc* d_objs = nullptr;
-    size_t objs_cap = 0;
-    LightDesc* d_lights = nullptr;
-    size_t lights_cap = 0;
+    DeviceBuf<TriHot> d_hot;
+    DeviceBuf<TriShade> d_shade;
+    DeviceBuf<TriCull> d_cull;
+    DeviceBuf<TriCull> d_tcull;  // kTraceSkipTris records: trace.hip's background skip
+    DeviceBuf<float> d_raw;
+    DeviceBuf<ObjectDesc> d_objs;
+    DeviceBuf<LightDesc> d_lights;
     // launch plans of eray_render_frames / eray_render_camera_path: HIP graphs of back-to-back
     // frames (chunks of up to kGraphFrames frames and remainders), each cached for the frame
     // parameters + stream + length + kind it was captured with; the least recently used is
     // evicted beyond kGraphCache
-    struct FrameGraph {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        std::vector<unsigned char> key;
-        uint64_t used = 0;
-    };
     std::vector<FrameGraph> graphs;
     uint64_t graph_clock = 0;
-    uint32_t* d_prog = nullptr;  // every object's texel program (MaterialDesc::prog), concatenated
-    size_t prog_cap = 0;
+    DeviceBuf<uint32_t> d_prog;  // every object's texel program (MaterialDesc::prog), concatenated
     std::vector<uint32_t> h_prog;
     std::vector<ObjectDesc> h_objs;  // kept alive for the async uploads
     std::vector<LightDesc> h_lights;
     std::vector<float> h_raw;
     std::vector<uint32_t> h_begin;   // obj_begin (nobj + 1) | objkey (nobj), uploaded with the descriptors
     uint32_t total_tris = 0;
+    uint32_t binned = 0;       // objects of more than kDirectMax faces (sync_scene)
     bool spec_pow = false;     // some material has a specular-power output
     bool example_mat = false;  // some material is main.rs's graph evaluated per hit
     // ---- per-camera setup (setup.hip, bins.hip), all on the device
-    CamDev* d_cam = nullptr;      // the context camera's device slot
-    CamState* d_state = nullptr;  // the last setup's results
-    CamState* h_state = nullptr;  // pinned host copy, valid once state_ev has completed
-    hipEvent_t state_ev = nullptr;
+    DeviceBuf<CamDev> d_cam;      // the context camera's device slot
+    DeviceBuf<CamState> d_state;  // the last setup's results
+    PinnedBuf<CamState> h_state;  // host copy, valid once state_ev has completed
+    Event state_ev;
     bool state_pending = false;   // a copy into h_state is in flight
     bool state_known = false;     // h_state holds the results of the setup of setup_key
     std::vector<uint64_t> setup_key;  // camera, size, rows and scene generation of the last setup
     std::vector<uint64_t> tcull_key;  // camera, size, scene generation and stream of d_tcull's records
     FrameSource setup_src;        // the last enqueued scene-camera setup: its source key and rows
-    ObjectDesc* h_objs_state = nullptr;  // pinned copy of the descriptors after that setup (pixel rectangles)
-    size_t h_objs_state_cap = 0;
+    PinnedBuf<ObjectDesc> h_objs_state;  // the descriptors after that setup (pixel rectangles)
     // where the frames in output buffers came from (eray_gather_frames): PPM slot address -> the
     // source of the last render enqueued into it, most recent last (at most kMaxTags)
     struct SlotTag {
@@ -143,77 +133,79 @@ struct eray_ctx {
     // rectangles — accumulated on the device (d_union_acc, captured into path graphs), then copied
     // into ring entry seq % kUnionRing on the device and the host, with an event per entry
     uint64_t path_seq = 0;
-    int32_t* d_union_acc = nullptr;
-    size_t union_cap = 0;  // objects per entry
-    int32_t* h_union = nullptr;
-    int32_t* d_union_host = nullptr;  // h_union's device address (mapped)
-    uint64_t union_seq[4] = {0, 0, 0, 0};
-    FrameSource union_src[4];
-    uint32_t union_nobj[4] = {0, 0, 0, 0};  // objects and scene generation the entry's union covers
-    uint64_t union_gen[4] = {0, 0, 0, 0};
-    hipEvent_t union_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DeviceBuf<int32_t> d_union_acc;
+    size_t union_cap() const { return d_union_acc.cap / 4; }  // objects per entry
+    PinnedBuf<int32_t> h_union;  // mapped: the flush kernel writes it through h_union.dev
+    uint64_t union_seq[kUnionRing] = {};
+    FrameSource union_src[kUnionRing];
+    uint32_t union_nobj[kUnionRing] = {};  // objects and scene generation the entry's union covers
+    uint64_t union_gen[kUnionRing] = {};
+    Event union_ev[kUnionRing];
     // eray_gather_frames' plan (comm.cpp owns it)
     void* gather_plan = nullptr;
     void (*gather_plan_free)(void*) = nullptr;
-    uint32_t* d_acc = nullptr;    // setup counter, partials and rectangle accumulators (enqueue_setup)
-    size_t acc_cap = 0;
-    uint32_t* d_begin = nullptr;  // obj_begin | objkey
-    size_t begin_cap = 0;
-    int4* d_range = nullptr;      // binned faces' bin rectangles, areas, binned-object index
-    unsigned long long* d_area = nullptr;
-    uint32_t* d_fkey = nullptr;
-    size_t face_cap = 0;
-    BinBuffers bins;
+    DeviceBuf<uint32_t> d_acc;    // setup counter, partials and rectangle accumulators (enqueue_setup)
+    DeviceBuf<uint32_t> d_begin;  // obj_begin | objkey
+    DeviceBuf<int4> d_range;      // binned faces' bin rectangles, areas, binned-object index
+    DeviceBuf<unsigned long long> d_area;
+    DeviceBuf<uint32_t> d_fkey;
+    BinBuffers bins;              // (bins.hip's own allocation: bins_alloc / bins_free)
     std::vector<uint64_t> bins_layout;
     uint64_t bins_gen = 0;        // bumped whenever bins_alloc (re)allocates the bin buffers
     size_t bin_cap = 0;           // entry capacity to allocate (grown when a setup overflows)
     bool rect_pairs = false;      // (diagnostics) setups walk the bin rectangles' pairs (bins.hip)
     // camera paths (eray_render_camera_path): the cameras of the current graph chunk on the
     // device, the whole path staged in pinned memory
-    CamDev* d_path = nullptr;
-    size_t path_cap = 0;
-    CamDev* d_path_all = nullptr;
-    size_t path_all_cap = 0;
+    DeviceBuf<CamDev> d_path;
+    DeviceBuf<CamDev> d_path_all;
     // two pinned staging buffers used in turn: a call waits only for the upload two calls back
     // (not for the previous call's frames, which its upload is queued behind)
-    CamDev* h_path[2] = {nullptr, nullptr};
-    size_t h_path_cap[2] = {0, 0};
-    hipEvent_t path_ev[2] = {nullptr, nullptr};  // each buffer's last upload (reusable once complete)
+    PinnedBuf<CamDev> h_path[2];
+    Event path_ev[2];  // each buffer's last upload (reusable once complete)
     uint32_t path_buf = 0;
     // batched setups of a path chunk's cameras (scenes without binned objects): per camera slot
     // its culling records, object descriptors and setup state
-    TriCull* d_bcull = nullptr;
-    size_t bcull_cap = 0;
-    ObjectDesc* d_bobjs = nullptr;
-    size_t bobjs_cap = 0;
-    CamState* d_bstate = nullptr;
-    size_t bstate_cap = 0;
+    DeviceBuf<TriCull> d_bcull;
+    DeviceBuf<ObjectDesc> d_bobjs;
+    DeviceBuf<CamState> d_bstate;
     // camera paths of scenes with binned objects: the setups of up to mc_k cameras in one
     // multi-camera build (SetupParams::ncam), into per-camera slices of a buffer set; two sets, so
     // that the next cameras' build (on mc_stream) runs beside the current cameras' frames
     struct MultiSet {
-        TriCull* cull = nullptr;
-        ObjectDesc* objs = nullptr;
-        CamState* state = nullptr;
-        uint32_t* acc = nullptr;
-        int4* range = nullptr;
-        unsigned long long* area = nullptr;
-        uint32_t* fkey = nullptr;
+        DeviceBuf<TriCull> cull;
+        DeviceBuf<ObjectDesc> objs;
+        DeviceBuf<CamState> state;
+        DeviceBuf<uint32_t> acc;
+        DeviceBuf<int4> range;
+        DeviceBuf<unsigned long long> area;
+        DeviceBuf<uint32_t> fkey;
         BinBuffers bins;
     };
     MultiSet mc[2];
     uint32_t mc_k = 0;
     std::vector<uint64_t> mc_layout;
     uint64_t mc_gen = 0;          // bumped whenever the multi-camera buffers are (re)allocated
-    hipStream_t mc_stream = nullptr;
-    hipEvent_t mc_fork = nullptr, mc_ready[2] = {nullptr, nullptr}, mc_free[2] = {nullptr, nullptr};
+    Stream mc_stream;
+    Event mc_fork, mc_ready[2], mc_free[2];
     // the latest render of the scene camera or of a camera path (tag_frames): what a scene-camera
     // gather plans for — state every rank holds alike when the ranks make the same render calls
     FrameSource gather_src;
-    uint8_t* d_coll = nullptr;     // kCollScratchBytes: the gathers' status exchanges (comm.cpp)
-    uint8_t* d_staging = nullptr;  // eray_gather_rows' banded staging (rank 0)
-    size_t staging_cap = 0;
-    LaunchCtx lc{nullptr, nullptr, nullptr};  // the separate fill's stream and events
+    DeviceBuf<uint8_t> d_coll;     // kCollScratchBytes: the gathers' status exchanges (comm.cpp)
+    DeviceBuf<uint8_t> d_staging;  // eray_gather_rows' banded staging (rank 0)
+    // the separate fill's stream and events, and the launchers' view of them
+    Stream fill_stream;
+    Event fill_fork, fill_join;
+    LaunchCtx lc{nullptr, nullptr, nullptr};
+
+    // Waits for the context's streams, then releases what the members do not own themselves.
+    ~eray_ctx() {
+        (void)hipSetDevice(device);
+        for (hipStream_t s : {stream, (hipStream_t)own_stream, (hipStream_t)mc_stream})
+            if (s) (void)hipStreamSynchronize(s);
+        if (gather_plan && gather_plan_free) gather_plan_free(gather_plan);  // (while the streams exist)
+        bins_free(bins);
+        for (auto& m : mc) bins_free(m.bins);
+    }
 };
 
 namespace {
@@ -245,20 +237,21 @@ int use_device(eray_ctx* ctx) {
     return ERAY_OK;
 }
 
+}  // namespace
+
+// (owners.hpp)
 template <typename T>
-int ensure(eray_ctx* ctx, T** ptr, size_t* cap, size_t need) {
-    if (need <= *cap && *ptr) return ERAY_OK;
-    if (*ptr) {
+int eray::gpu::DeviceBuf<T>::ensure(eray_ctx* ctx, size_t need) {
+    if (need <= this->cap && this->p_) return ERAY_OK;
+    if (this->p_) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(*ptr));
-        *ptr = nullptr;
-        *cap = 0;
+        HIP_TRY(ctx, this->release());
     }
-    size_t n = need ? need : 1;
-    HIP_TRY(ctx, hipMalloc((void**)ptr, n * sizeof(T)));
-    *cap = n;
+    HIP_TRY(ctx, alloc(need ? need : 1));
     return ERAY_OK;
 }
+
+namespace {
 
 uint32_t sat_u32_host(float f) {
     if (!(f > 0.0f)) return 0u;
@@ -277,23 +270,10 @@ int sync_scene(eray_ctx* ctx) {
         uint32_t T = 0;
         for (auto& o : ctx->objects) T += o.T;
         ctx->total_tris = T;
-        if ((st = ensure(ctx, &ctx->d_hot, &ctx->tri_cap, T))) return st;
-        size_t shade_cap = ctx->tri_cap;
-        // shade shares the capacity bookkeeping of hot: (re)allocate alongside
-        if (ctx->d_shade) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipFree(ctx->d_shade));
-            ctx->d_shade = nullptr;
-        }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_shade, shade_cap * sizeof(TriShade)));
-        if (ctx->d_cull) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipFree(ctx->d_cull));
-            ctx->d_cull = nullptr;
-        }
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_cull, shade_cap * sizeof(TriCull)));
-        if (!ctx->d_tcull)  // the general tracer's per-frame culling records (small scenes)
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_tcull, kTraceSkipTris * sizeof(TriCull)));
+        if ((st = ctx->d_hot.ensure(ctx, T)) || (st = ctx->d_shade.ensure(ctx, T)) || (st = ctx->d_cull.ensure(ctx, T)))
+            return st;
+        // the general tracer's per-frame culling records (small scenes)
+        if ((st = ctx->d_tcull.ensure(ctx, kTraceSkipTris))) return st;
 
         ctx->h_raw.assign((size_t)T * 24, 0.0f);
         size_t off = 0;
@@ -305,7 +285,7 @@ int sync_scene(eray_ctx* ctx) {
                         sizeof(float) * 6 * o.T);
             off += o.T;
         }
-        if ((st = ensure(ctx, &ctx->d_raw, &ctx->raw_cap, (size_t)T * 24))) return st;
+        if ((st = ctx->d_raw.ensure(ctx, (size_t)T * 24))) return st;
         if (T) {
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw, ctx->h_raw.data(), sizeof(float) * 24 * (size_t)T,
                                         hipMemcpyHostToDevice, ctx->stream));
@@ -346,7 +326,7 @@ int sync_scene(eray_ctx* ctx) {
             ctx->h_prog.insert(ctx->h_prog.end(), w, w + ins.size() * (sizeof(TexelInstr) / 4));
         }
         if (!ctx->h_prog.empty()) {
-            if ((st = ensure(ctx, &ctx->d_prog, &ctx->prog_cap, ctx->h_prog.size()))) return st;
+            if ((st = ctx->d_prog.ensure(ctx, ctx->h_prog.size()))) return st;
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prog, ctx->h_prog.data(), 4 * ctx->h_prog.size(), hipMemcpyHostToDevice,
                                         ctx->stream));
         }
@@ -401,8 +381,8 @@ int sync_scene(eray_ctx* ctx) {
             d.brightness = l.brightness;
             ctx->h_lights.push_back(d);
         }
-        if ((st = ensure(ctx, &ctx->d_objs, &ctx->objs_cap, ctx->h_objs.size()))) return st;
-        if ((st = ensure(ctx, &ctx->d_lights, &ctx->lights_cap, ctx->h_lights.size()))) return st;
+        if ((st = ctx->d_objs.ensure(ctx, ctx->h_objs.size()))) return st;
+        if ((st = ctx->d_lights.ensure(ctx, ctx->h_lights.size()))) return st;
         if (!ctx->h_objs.empty())
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_objs, ctx->h_objs.data(), sizeof(ObjectDesc) * ctx->h_objs.size(),
                                         hipMemcpyHostToDevice, ctx->stream));
@@ -418,26 +398,21 @@ int sync_scene(eray_ctx* ctx) {
             ctx->h_begin[i] = ctx->h_objs[i].g.tri_begin;
             ctx->h_begin[nobj + 1 + i] = ctx->objects[i].T > kDirectMax ? nb++ : ~0u;
         }
+        ctx->binned = nb;
         ctx->h_begin[nobj] = ctx->total_tris;
-        if ((st = ensure(ctx, &ctx->d_begin, &ctx->begin_cap, ctx->h_begin.size()))) return st;
+        if ((st = ctx->d_begin.ensure(ctx, ctx->h_begin.size()))) return st;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_begin, ctx->h_begin.data(), 4 * ctx->h_begin.size(), hipMemcpyHostToDevice,
                                     ctx->stream));
         // rectangle accumulators + the setup's workgroup counter, zero between setups
         const size_t acc_words = 4 * (size_t)nobj + 1 + 10 * (size_t)kSetupMaxBlocks;
-        if (ctx->acc_cap < acc_words || !ctx->d_acc) {
-            if ((st = ensure(ctx, &ctx->d_acc, &ctx->acc_cap, acc_words))) return st;
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_acc, 0, 4 * ctx->acc_cap, ctx->stream));
+        if (ctx->d_acc.cap < acc_words) {
+            if ((st = ctx->d_acc.ensure(ctx, acc_words))) return st;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_acc, 0, 4 * ctx->d_acc.cap, ctx->stream));
         }
         ctx->desc_dirty = false;
         ++ctx->scene_gen;
     }
     return ERAY_OK;
-}
-
-uint32_t binned_objects(const eray_ctx* ctx) {
-    uint32_t nb = 0;
-    for (auto& o : ctx->objects) nb += o.T > kDirectMax;
-    return nb;
 }
 
 // The device buffers of the binned objects' bins for this camera size, row phase and rows
@@ -464,16 +439,10 @@ uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) 
     return h;
 }
 
-// The source tag of a render of the scene camera over rows rs: a hash of the camera's value, the
-// scene generation (uploads since the context was made) and Camera::size — what every rank that
-// made the same scene calls computes alike.
-FrameSource scene_source(const eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
+FrameSource frame_source(uint32_t kind, uint64_t key, uint32_t W, uint32_t H, const RowSpan& rs) {
     FrameSource s;
-    s.kind = kSrcScene;
-    uint64_t h = fnv1a(&ctx->camera, sizeof ctx->camera);
-    h = fnv1a(&ctx->scene_gen, sizeof ctx->scene_gen, h);
-    const uint32_t wh[2] = {W, H};
-    s.key = fnv1a(wh, sizeof wh, h);
+    s.kind = kind;
+    s.key = key;
     s.W = W;
     s.H = H;
     s.row0 = rs.row0;
@@ -481,6 +450,16 @@ FrameSource scene_source(const eray_ctx* ctx, uint32_t W, uint32_t H, const RowS
     s.band_shift = rs.band_shift;
     s.band_stride = rs.band_stride;
     return s;
+}
+
+// The source tag of a render of the scene camera over rows rs: a hash of the camera's value, the
+// scene generation (uploads since the context was made) and Camera::size — what every rank that
+// made the same scene calls computes alike.
+FrameSource scene_source(const eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
+    uint64_t h = fnv1a(&ctx->camera, sizeof ctx->camera);
+    h = fnv1a(&ctx->scene_gen, sizeof ctx->scene_gen, h);
+    const uint32_t wh[2] = {W, H};
+    return frame_source(kSrcScene, fnv1a(wh, sizeof wh, h), W, H, rs);
 }
 
 // A tagged slot's PPM bytes: [ppm, ppm + rows * W * 3).
@@ -519,14 +498,11 @@ void binned_lists(const eray_ctx* ctx, std::vector<uint32_t>* kbegin, std::vecto
 
 int ensure_bins(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
     const uint32_t row0 = rs.row0, rows = rs.rows;
-    const uint32_t nb = binned_objects(ctx);
+    const uint32_t nb = ctx->binned;
     const uint32_t T = ctx->total_tris;
-    if (ctx->face_cap < T || !ctx->d_range) {
-        int st;
-        if ((st = ensure(ctx, &ctx->d_range, &ctx->face_cap, T))) return st;
-        size_t c1 = 0, c2 = 0;
-        if ((st = ensure(ctx, &ctx->d_area, &c1, T)) || (st = ensure(ctx, &ctx->d_fkey, &c2, T))) return st;
-    }
+    int st;
+    if ((st = ctx->d_range.ensure(ctx, T)) || (st = ctx->d_area.ensure(ctx, T)) || (st = ctx->d_fkey.ensure(ctx, T)))
+        return st;
     size_t binned_tris = 0;
     for (auto& o : ctx->objects)
         if (o.T > kDirectMax) binned_tris += o.T;
@@ -569,7 +545,7 @@ SetupParams setup_params(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint
     sp.done = ctx->d_acc;
     sp.part = ctx->d_acc + 1;
     sp.acc = ctx->d_acc + 1 + 10 * (size_t)kSetupMaxBlocks;
-    const bool binned = binned_objects(ctx) > 0;
+    const bool binned = ctx->binned > 0;
     sp.binned = binned ? 1u : 0u;
     sp.rect_pairs = ctx->rect_pairs ? 1u : 0u;
     if (binned) {
@@ -613,14 +589,14 @@ int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
         // (a priority of its own: HIP deals its hardware queues to streams round-robin per priority,
         // and on the frames' queue the setup chain serialised with them — moving C5 frame 416 ->
         // 375 us, 3840x2160 / 70k 60.6 -> 55.7 us, profiles/r04/ab/ab_r04m.txt)
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->mc_stream, hipStreamNonBlocking, -1));
-        for (hipEvent_t* ev : {&ctx->mc_fork, &ctx->mc_ready[0], &ctx->mc_ready[1], &ctx->mc_free[0], &ctx->mc_free[1]})
-            HIP_TRY(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        HIP_TRY(ctx, ctx->mc_stream.create(hipStreamNonBlocking, -1));
+        for (Event* ev : {&ctx->mc_fork, &ctx->mc_ready[0], &ctx->mc_ready[1], &ctx->mc_free[0], &ctx->mc_free[1]})
+            HIP_TRY(ctx, ev->create(hipEventDisableTiming));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->mc_stream));
     ctx->mc_layout.clear();
-    const uint32_t T = ctx->total_tris, nobj = (uint32_t)ctx->objects.size(), nb = binned_objects(ctx);
+    const uint32_t T = ctx->total_tris, nobj = (uint32_t)ctx->objects.size(), nb = ctx->binned;
     const size_t t = (size_t)K * (T ? T : 1);
     const size_t acc_words = 4 * (size_t)K * nobj + 1 + 10 * (size_t)kSetupMaxBlocks;
     // camera k's copy of binned object j: key k * nb + j, its faces from k * T + tri_begin
@@ -632,23 +608,11 @@ int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
             mobj.push_back(k * nobj + kobj[j]);
         }
     for (auto& m : ctx->mc) {
-        for (void* b : {(void*)m.cull, (void*)m.objs, (void*)m.state, (void*)m.acc, (void*)m.range, (void*)m.area,
-                        (void*)m.fkey})
-            if (b) HIP_TRY(ctx, hipFree(b));
-        m.cull = nullptr;
-        m.objs = nullptr;
-        m.state = nullptr;
-        m.acc = nullptr;
-        m.range = nullptr;
-        m.area = nullptr;
-        m.fkey = nullptr;
-        HIP_TRY(ctx, hipMalloc((void**)&m.cull, sizeof(TriCull) * t));
-        HIP_TRY(ctx, hipMalloc((void**)&m.objs, sizeof(ObjectDesc) * K * (nobj ? nobj : 1)));
-        HIP_TRY(ctx, hipMalloc((void**)&m.state, sizeof(CamState) * K));
-        HIP_TRY(ctx, hipMalloc((void**)&m.acc, 4 * acc_words));
-        HIP_TRY(ctx, hipMalloc((void**)&m.range, sizeof(int4) * t));
-        HIP_TRY(ctx, hipMalloc((void**)&m.area, sizeof(unsigned long long) * t));
-        HIP_TRY(ctx, hipMalloc((void**)&m.fkey, sizeof(uint32_t) * t));
+        int st;
+        if ((st = m.cull.ensure(ctx, t)) || (st = m.objs.ensure(ctx, (size_t)K * nobj)) || (st = m.state.ensure(ctx, K)) ||
+            (st = m.acc.ensure(ctx, acc_words)) || (st = m.range.ensure(ctx, t)) || (st = m.area.ensure(ctx, t)) ||
+            (st = m.fkey.ensure(ctx, t)))
+            return st;
         HIP_TRY(ctx, hipMemsetAsync(m.acc, 0, 4 * acc_words, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(m.state, 0, sizeof(CamState) * K, ctx->stream));
         for (uint32_t k = 0; k < K && nobj; ++k)  // (each setup rewrites the rectangles and bin views)
@@ -673,7 +637,7 @@ int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_ca
     sp.ncam = ncam;
     sp.T1 = T;
     sp.nobj1 = nobj;
-    sp.nb1 = binned_objects(ctx);
+    sp.nb1 = ctx->binned;
     sp.T = ncam * T;
     sp.nobj = ncam * nobj;
     sp.cull = m.cull;
@@ -703,7 +667,7 @@ int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_ca
 // as the frame.  Up to kBatchTris triangles (the slots hold kGraphFrames x T culling records).
 constexpr uint32_t kBatchTris = 16384;
 bool batch_setup_ok(const eray_ctx* ctx) {
-    return !binned_objects(ctx) && ctx->objects.size() <= kSetupBatchMaxObjects && ctx->total_tris <= kBatchTris;
+    return !ctx->binned && ctx->objects.size() <= kSetupBatchMaxObjects && ctx->total_tris <= kBatchTris;
 }
 
 CamDev cam_dev(const eray_camera& c) {
@@ -736,7 +700,7 @@ int sync_setup(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs, bool wa
             else if (q != hipErrorNotReady) return set_error(ctx, ERAY_E_HIP, "setup event: %s", hipGetErrorString(q));
         }
         auto bins_ready = [&]() -> int {
-            if (!binned_objects(ctx)) return ERAY_OK;
+            if (!ctx->binned) return ERAY_OK;
             const std::vector<uint64_t> before = ctx->bins_layout;
             if (int st = ensure_bins(ctx, W, H, rs)) return st;
             if (ctx->bins_layout != before)  // new buffers: the bin statistics start over
@@ -764,13 +728,7 @@ int sync_setup(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs, bool wa
             // the objects' pixel rectangles of this camera (eray_gather_frames' transfer layout);
             // no copy into the pinned buffer is in flight here (state_pending was drained above)
             const size_t nobj = ctx->objects.size();
-            if (ctx->h_objs_state_cap < nobj) {
-                if (ctx->h_objs_state) HIP_TRY(ctx, hipHostFree(ctx->h_objs_state));
-                ctx->h_objs_state = nullptr;
-                ctx->h_objs_state_cap = 0;
-                HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_objs_state, sizeof(ObjectDesc) * nobj, hipHostMallocDefault));
-                ctx->h_objs_state_cap = nobj;
-            }
+            if (ctx->h_objs_state.cap < nobj) HIP_TRY(ctx, ctx->h_objs_state.alloc(nobj));
             if (nobj)
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->h_objs_state, ctx->d_objs, sizeof(ObjectDesc) * nobj,
                                             hipMemcpyDeviceToHost, ctx->stream));
@@ -810,73 +768,35 @@ int eray_ctx_create(int device, eray_ctx** out) {
     if (!ctx) return set_error(nullptr, ERAY_E_OUT_OF_MEMORY, "context allocation failed");
     ctx->device = device;
     e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = ctx->own_stream.create(hipStreamNonBlocking);
+    ctx->stream = ctx->own_stream;
     // the separate fill kernel's stream and fork / join events (render.hip launch_frame_kernel);
     // low priority, so that it never shares a hardware queue with a caller's normal-priority
     // stream (the fill would then wait for the frame kernel it runs beside)
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&ctx->lc.side, hipStreamNonBlocking, 1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lc.fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->lc.join, hipEventDisableTiming);
+    if (e == hipSuccess) e = ctx->fill_stream.create(hipStreamNonBlocking, 1);
+    if (e == hipSuccess) e = ctx->fill_fork.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = ctx->fill_join.create(hipEventDisableTiming);
+    ctx->lc = LaunchCtx{ctx->fill_stream, ctx->fill_fork, ctx->fill_join};
     // the per-camera setup's device state and its pinned host copy
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_cam, sizeof(CamDev));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_state, sizeof(CamState));
+    if (e == hipSuccess) e = ctx->d_cam.alloc(1);
+    if (e == hipSuccess) e = ctx->d_state.alloc(1);
     if (e == hipSuccess) e = hipMemset(ctx->d_state, 0, sizeof(CamState));
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_coll, kCollScratchBytes);
+    if (e == hipSuccess) e = ctx->d_coll.alloc(kCollScratchBytes);
 
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_state, sizeof(CamState), hipHostMallocDefault);
+    if (e == hipSuccess) e = ctx->h_state.alloc(1);
     if (e == hipSuccess) std::memset(ctx->h_state, 0, sizeof(CamState));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->state_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->path_ev[0], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->path_ev[1], hipEventDisableTiming);
+    for (Event* ev : {&ctx->state_ev, &ctx->path_ev[0], &ctx->path_ev[1]})
+        if (e == hipSuccess) e = ev->create(hipEventDisableTiming);
     if (e != hipSuccess) {
-        ctx->stream = ctx->own_stream;
-        eray_ctx_destroy(ctx);
+        delete ctx;
         return set_error(nullptr, ERAY_E_HIP, "context init: %s", hipGetErrorString(e));
     }
-    ctx->stream = ctx->own_stream;
     *out = ctx;
     return ERAY_OK;
 }
 
 int eray_ctx_destroy(eray_ctx* ctx) {
-    if (!ctx) return ERAY_OK;
-    hipSetDevice(ctx->device);
-    if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    if (ctx->own_stream) hipStreamSynchronize(ctx->own_stream);
-    bins_free(ctx->bins);
-    if (ctx->mc_stream) hipStreamSynchronize(ctx->mc_stream);
-    for (auto& m : ctx->mc) {
-        bins_free(m.bins);
-        for (void* b : {(void*)m.cull, (void*)m.objs, (void*)m.state, (void*)m.acc, (void*)m.range, (void*)m.area,
-                        (void*)m.fkey})
-            if (b) hipFree(b);
-    }
-    for (hipEvent_t ev : {ctx->mc_fork, ctx->mc_ready[0], ctx->mc_ready[1], ctx->mc_free[0], ctx->mc_free[1]})
-        if (ev) hipEventDestroy(ev);
-    if (ctx->mc_stream) hipStreamDestroy(ctx->mc_stream);
-    void* bufs[] = {ctx->d_hot,   ctx->d_shade, ctx->d_cull,  ctx->d_raw,  ctx->d_objs,  ctx->d_lights,
-                    ctx->d_prog,  ctx->d_cam,   ctx->d_state, ctx->d_acc,  ctx->d_begin, ctx->d_range,
-                    ctx->d_area,  ctx->d_fkey,  ctx->d_path,  ctx->d_path_all, ctx->d_staging,
-                    ctx->d_bcull, ctx->d_bobjs, ctx->d_bstate, ctx->d_tcull, ctx->d_union_acc, ctx->d_coll};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    if (ctx->h_state) hipHostFree(ctx->h_state);
-    for (CamDev* h : ctx->h_path)
-        if (h) hipHostFree(h);
-    if (ctx->h_objs_state) hipHostFree(ctx->h_objs_state);
-    if (ctx->h_union) hipHostFree(ctx->h_union);
-    for (hipEvent_t ev : ctx->union_ev)
-        if (ev) hipEventDestroy(ev);
-    if (ctx->gather_plan && ctx->gather_plan_free) ctx->gather_plan_free(ctx->gather_plan);
-    for (auto& g : ctx->graphs) {
-        if (g.exec) hipGraphExecDestroy(g.exec);
-        if (g.graph) hipGraphDestroy(g.graph);
-    }
-    for (hipEvent_t ev : {ctx->state_ev, ctx->path_ev[0], ctx->path_ev[1], ctx->lc.fork, ctx->lc.join})
-        if (ev) hipEventDestroy(ev);
-    if (ctx->lc.side) hipStreamDestroy(ctx->lc.side);
-    if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;  // (~eray_ctx waits for its streams)
     return ERAY_OK;
 }
 
@@ -1182,7 +1102,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     *empty = !rp->rows || !W;
     if (*empty) return ERAY_OK;
     // the general tracer's camera rays scan the binned objects' bins (a setup of its own kind)
-    const bool trace_bins = general && !(rp->flags & ERAY_RENDER_BRUTE_FORCE) && binned_objects(ctx) > 0;
+    const bool trace_bins = general && !(rp->flags & ERAY_RENDER_BRUTE_FORCE) && ctx->binned > 0;
     bool known = true;
     if (cull || trace_bins)
         if (int st = sync_setup(ctx, W, H, row_span(rp), wait == SetupWait::kYes, &known, trace_bins)) return st;
@@ -1266,7 +1186,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
         }
         return ERAY_OK;
     }
-    if (binned_objects(ctx)) {  // the detail sub-block list of the setup (ordered: heavy ones first)
+    if (ctx->binned) {  // the detail sub-block list of the setup (ordered: heavy ones first)
         p.detail_list = ctx->bins.dlist;
         p.detail_occ = ctx->bins.docc;
         p.detail_heavy = ctx->bins.dcount;
@@ -1313,14 +1233,19 @@ constexpr uint32_t kGraphFrames = 64;
 
 constexpr size_t kGraphCache = 6;
 
+// Appends v's bytes to a graph key.
+template <typename V>
+void append(std::vector<unsigned char>& key, const V& v) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(&v);
+    key.insert(key.end(), b, b + sizeof v);
+}
+
 // The graph of n back-to-back frames, frame f enqueued by body(f), for `key` (+ n and the
 // stream), captured unless cached.
 template <typename Body>
 int ensure_graph(eray_ctx* ctx, std::vector<unsigned char> key, uint32_t n, Body&& body, hipGraphExec_t* out) {
-    const size_t at = key.size();
-    key.resize(at + sizeof n + sizeof ctx->stream);
-    std::memcpy(key.data() + at, &n, sizeof n);
-    std::memcpy(key.data() + at + sizeof n, &ctx->stream, sizeof ctx->stream);
+    append(key, n);
+    append(key, ctx->stream);
     for (auto& G : ctx->graphs)
         if (G.key == key) {
             G.used = ++ctx->graph_clock;
@@ -1331,49 +1256,39 @@ int ensure_graph(eray_ctx* ctx, std::vector<unsigned char> key, uint32_t n, Body
         size_t lru = 0;
         for (size_t i = 1; i < ctx->graphs.size(); ++i)
             if (ctx->graphs[i].used < ctx->graphs[lru].used) lru = i;
-        auto& G = ctx->graphs[lru];
-        if (G.exec) hipGraphExecDestroy(G.exec);
-        if (G.graph) hipGraphDestroy(G.graph);
-        ctx->graphs.erase(ctx->graphs.begin() + (std::ptrdiff_t)lru);
+        std::swap(ctx->graphs[lru], ctx->graphs.back());
+        ctx->graphs.pop_back();
     }
     HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     int st = ERAY_OK;
     for (uint32_t f = 0; f < n && st == ERAY_OK; ++f) st = body(f, n);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-    if (st != ERAY_OK) {
-        if (g) hipGraphDestroy(g);
-        return st;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (e == hipSuccess) e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    FrameGraph G;
+    hipError_t e = hipStreamEndCapture(ctx->stream, G.graph.put());
+    if (st != ERAY_OK) return st;
+    if (e == hipSuccess) e = hipGraphInstantiate(G.exec.put(), G.graph, nullptr, nullptr, 0);
     // the executable's packets and arguments go to the device now, not at its first launch (a
     // plan prepared ahead of a timed loop otherwise pays ~20 us at its first replay)
-    if (e == hipSuccess) e = hipGraphUpload(exec, ctx->stream);
-    if (e != hipSuccess) {
-        if (g) hipGraphDestroy(g);
-        return set_error(ctx, ERAY_E_HIP, "frame graph capture: %s", hipGetErrorString(e));
-    }
-    eray_ctx::FrameGraph G;
-    G.graph = g;
-    G.exec = exec;
+    if (e == hipSuccess) e = hipGraphUpload(G.exec, ctx->stream);
+    if (e != hipSuccess) return set_error(ctx, ERAY_E_HIP, "frame graph capture: %s", hipGetErrorString(e));
     G.key = std::move(key);
     G.used = ++ctx->graph_clock;
+    *out = G.exec;
     ctx->graphs.push_back(std::move(G));
-    *out = exec;
     return ERAY_OK;
 }
 
 std::vector<unsigned char> params_key(const FrameParams& p, uint32_t kind) {
-    std::vector<unsigned char> key(sizeof p + sizeof kind);
-    std::memcpy(key.data(), &p, sizeof p);
-    std::memcpy(key.data() + sizeof p, &kind, sizeof kind);
+    std::vector<unsigned char> key;
+    key.reserve(sizeof p + sizeof kind + 128);  // (room for what the callers append: one allocation)
+    append(key, p);
+    append(key, kind);
     return key;
 }
 
 // The launch plan of `frames` frames: a graph of `chunk` = min(frames, kGraphFrames) frames,
 // replayed frames / chunk times, and a graph of the remainder (no plain launches, whose host
 // cost can exceed a frame's device time).  chunk = 0: plain launches (null stream, 1 frame).
+// A chunk without a graph (direct_plan) is enqueued frame by frame.
 struct Plan {
     uint32_t chunk = 0, rest = 0;
     hipGraphExec_t chunk_exec = nullptr, rest_exec = nullptr;
@@ -1392,48 +1307,107 @@ int ensure_plan(eray_ctx* ctx, const std::vector<unsigned char>& key, uint32_t f
     }
     return ERAY_OK;
 }
+// The same chunks with no graphs.
+Plan direct_plan(uint32_t frames) {
+    Plan plan;
+    plan.chunk = std::min(frames, kGraphFrames);
+    plan.rest = frames % plan.chunk;
+    return plan;
+}
 
-// Replays `plan` for `frames` frames (before_chunk(first frame, count) runs ahead of each graph
-// launch, plain(f) renders frames the plan does not cover); mean device time per frame when asked.
-template <typename Before, typename Plain>
-int replay(eray_ctx* ctx, const Plan& plan, uint32_t frames, Before&& before_chunk, Plain&& plain, float* mean_ms) {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (mean_ms) {
-        *mean_ms = 0.0f;
-        for (auto& e : ev) {
-            hipError_t he = hipEventCreate(&e);
-            if (he != hipSuccess) {
-                if (ev[0]) hipEventDestroy(ev[0]);
-                return set_error(ctx, ERAY_E_HIP, "hipEventCreate: %s", hipGetErrorString(he));
-            }
-        }
-    }
-    int st = ERAY_OK;
-    hipError_t he = mean_ms ? hipEventRecord(ev[0], ctx->stream) : hipSuccess;
+// Runs `plan` for `frames` frames of `run`: run.before_chunk(first frame, count) ahead of each
+// chunk, the chunk as its graph's launch or, without one, run.body(first, f, count) per frame
+// f < count; run.plain(f) renders the frames the plan does not cover.
+template <typename Run>
+int replay(eray_ctx* ctx, const Plan& plan, uint32_t frames, const Run& run) {
     uint32_t done = 0;
-    for (; plan.chunk && done + plan.chunk <= frames && he == hipSuccess && !st; done += plan.chunk) {
-        st = before_chunk(done, plan.chunk);
-        if (!st) he = hipGraphLaunch(plan.chunk_exec, ctx->stream);
-    }
-    if (plan.rest && done + plan.rest == frames && he == hipSuccess && !st) {
-        st = before_chunk(done, plan.rest);
-        if (!st) he = hipGraphLaunch(plan.rest_exec, ctx->stream);
-        done += plan.rest;
-    }
-    for (; done < frames && he == hipSuccess && !st; ++done) st = plain(done);
-    if (mean_ms && he == hipSuccess && !st) {
-        he = hipEventRecord(ev[1], ctx->stream);
-        if (he == hipSuccess) he = hipEventSynchronize(ev[1]);
-        float ms = 0.0f;
-        if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        if (he == hipSuccess) *mean_ms = ms / (float)frames;
-    }
-    for (auto e : ev)
-        if (e) hipEventDestroy(e);
-    if (st) return st;
-    if (he != hipSuccess) return set_error(ctx, ERAY_E_HIP, "render loop: %s", hipGetErrorString(he));
+    auto chunk = [&](uint32_t count, hipGraphExec_t exec) -> int {
+        if (int st = run.before_chunk(done, count)) return st;
+        if (exec) {
+            const hipError_t e = hipGraphLaunch(exec, ctx->stream);
+            if (e != hipSuccess) return set_error(ctx, ERAY_E_HIP, "render loop: %s", hipGetErrorString(e));
+        } else {
+            for (uint32_t f = 0; f < count; ++f)
+                if (int st = run.body(done, f, count)) return st;
+        }
+        done += count;
+        return ERAY_OK;
+    };
+    while (plan.chunk && done + plan.chunk <= frames)
+        if (int st = chunk(plan.chunk, plan.chunk_exec)) return st;
+    if (plan.rest && done + plan.rest == frames)
+        if (int st = chunk(plan.rest, plan.rest_exec)) return st;
+    for (; done < frames; ++done)
+        if (int st = run.plain(done)) return st;
     return ERAY_OK;
 }
+
+// The device time of a stretch of work on a stream, between two events of its own.
+struct TimedRegion {
+    Event ev[2];
+    hipStream_t stream = nullptr;
+    hipError_t begin(hipStream_t s) {
+        stream = s;
+        hipError_t e = ev[0].create();
+        if (e == hipSuccess) e = ev[1].create();
+        return e == hipSuccess ? hipEventRecord(ev[0], stream) : e;
+    }
+    hipError_t end(float* ms) {  // waits for the work
+        hipError_t e = hipEventRecord(ev[1], stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
+        return e == hipSuccess ? hipEventElapsedTime(ms, ev[0], ev[1]) : e;
+    }
+};
+// work() enqueues `frames` frames on the context's stream; their mean device time when asked.
+template <typename Work>
+int timed_frames(eray_ctx* ctx, uint32_t frames, float* mean_ms, Work&& work) {
+    TimedRegion t;
+    if (mean_ms) {
+        *mean_ms = 0.0f;
+        HIP_TRY(ctx, t.begin(ctx->stream));
+    }
+    if (int st = work()) return st;
+    if (mean_ms) {
+        float ms = 0.0f;
+        HIP_TRY(ctx, t.end(&ms));
+        *mean_ms = ms / (float)frames;
+    }
+    return ERAY_OK;
+}
+
+// The start / end events of `launches` dispatch-timed launches (eray_time_frames_ring,
+// eray_time_write_ceiling), `per` events each: the frame kernel's pair first.
+struct LaunchTimers {
+    std::vector<Event> ev;
+    uint32_t launches, per;
+    LaunchTimers(uint32_t launches, uint32_t per) : ev((size_t)launches * per), launches(launches), per(per) {}
+    hipError_t create() {
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < ev.size() && e == hipSuccess; ++k) e = ev[k].create();
+        return e;
+    }
+    hipEvent_t at(uint32_t l, uint32_t k) const { return ev[(size_t)l * per + k]; }
+    // The launches' frame kernel times into out's launches / frames_per_launch / mean / min / max
+    // (after the stream has been synchronised).
+    hipError_t reduce(uint32_t frames_per_launch, eray_kernel_times* out) const {
+        double sum = 0.0;
+        float lo = 0.0f, hi = 0.0f;
+        for (uint32_t l = 0; l < launches; ++l) {
+            float k = 0.0f;
+            const hipError_t e = hipEventElapsedTime(&k, at(l, 0), at(l, 1));
+            if (e != hipSuccess) return e;
+            sum += k;
+            lo = l ? std::min(lo, k) : k;
+            hi = l ? std::max(hi, k) : k;
+        }
+        out->launches = launches;
+        out->frames_per_launch = frames_per_launch;
+        out->frame_kernel_ms = (float)(sum / launches);
+        out->frame_kernel_min_ms = lo;
+        out->frame_kernel_max_ms = hi;
+        return hipSuccess;
+    }
+};
 // Frames in flight (eray_frame_ring): frames of one call are rendered `per_launch` to a kernel
 // launch (FrameParams::nframes), frame k into ring slot k % slots.
 struct Ring {
@@ -1511,52 +1485,62 @@ FrameParams ring_frames(const FrameParams& p, const Ring& r, uint32_t f, uint32_
 }
 
 std::vector<unsigned char> ring_key(std::vector<unsigned char> key, const Ring& r) {
-    const size_t at = key.size();
-    key.resize(at + sizeof r);
-    std::memcpy(key.data() + at, &r, sizeof r);
+    append(key, r);
     return key;
 }
-}  // namespace
+
+// The frames of a call with the scene camera into a ring: frame f is rendered by the launch of
+// frame f - f % per_launch.
+struct StaticRing {
+    eray_ctx* ctx;
+    const FrameParams& p;
+    const Ring& r;
+    uint32_t frames;
+    int plan(Plan* out) const {
+        auto frame = [this](uint32_t f, uint32_t n) { return body(0, f, n); };
+        return ensure_plan(ctx, ring_key(params_key(p, 0), r), frames, frame, out);
+    }
+    int before_chunk(uint32_t, uint32_t) const { return ERAY_OK; }
+    int body(uint32_t, uint32_t f, uint32_t n) const {
+        if (f % r.per_launch) return ERAY_OK;
+        HIP_TRY(ctx, launch_frame(ctx, ring_frames(p, r, f, std::min(r.per_launch, n - f))));
+        return ERAY_OK;
+    }
+    int plain(uint32_t f) const { return body(0, f, frames); }
+};
 
 // The camera-path rectangle union (eray_gather_frames' layout of path frames): the device
 // accumulator for nobj objects (SetupParams::path_union: the path's setup kernels fold every
 // camera's rectangles into it) and a ring of kUnionRing finished unions in mapped pinned memory.
 int ensure_union(eray_ctx* ctx, uint32_t nobj) {
-    if (ctx->d_union_acc && ctx->union_cap >= nobj) return ERAY_OK;
-    for (hipEvent_t& ev : ctx->union_ev) {
-        if (!ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (ctx->d_union_acc && ctx->h_union && ctx->union_cap() >= nobj) return ERAY_OK;
+    for (Event& ev : ctx->union_ev) {
+        if (!ev) HIP_TRY(ctx, ev.create(hipEventDisableTiming));
         HIP_TRY(ctx, hipEventSynchronize(ev));  // (a flush into the ring still in flight)
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_union_acc) HIP_TRY(ctx, hipFree(ctx->d_union_acc));
-    if (ctx->h_union) HIP_TRY(ctx, hipHostFree(ctx->h_union));
-    ctx->d_union_acc = nullptr;
-    ctx->h_union = nullptr;
-    ctx->d_union_host = nullptr;
-    ctx->union_cap = 0;
     const uint32_t n = std::max<uint32_t>(nobj, 1u);
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_union_acc, 4 * sizeof(int32_t) * n));
-    HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_union, 4 * sizeof(int32_t) * n * kUnionRing, hipHostMallocMapped));
-    HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->d_union_host, ctx->h_union, 0));
+    HIP_TRY(ctx, ctx->d_union_acc.alloc(4 * (size_t)n));
+    HIP_TRY(ctx, ctx->h_union.alloc(4 * (size_t)n * kUnionRing, hipHostMallocMapped));
     HIP_TRY(ctx, launch_union_flush(ctx->d_union_acc, n, nullptr, ctx->stream));  // the initial reset
     for (auto& s : ctx->union_seq) s = 0;
-    ctx->union_cap = n;
     return ERAY_OK;
 }
-// After path call `seq`'s frames: its union into ring entry seq % kUnionRing (and the accumulator
-// reset for the next path), one kernel on the stream.
-int finish_union(eray_ctx* ctx, uint64_t seq, const FrameSource& src, uint32_t nobj) {
-    const uint32_t e = (uint32_t)(seq % kUnionRing);
+// After the frames of path call `src` (key: its sequence number): its union into ring entry
+// key % kUnionRing (and the accumulator reset for the next path), one kernel on the stream.
+int finish_union(eray_ctx* ctx, const FrameSource& src, uint32_t nobj) {
+    const uint32_t e = (uint32_t)(src.key % kUnionRing);
     HIP_TRY(ctx, hipEventSynchronize(ctx->union_ev[e]));  // the entry's flush kUnionRing paths back
     HIP_TRY(ctx, launch_union_flush(ctx->d_union_acc, std::max(nobj, 1u),
-                                    ctx->d_union_host + (size_t)e * 4 * ctx->union_cap, ctx->stream));
+                                    ctx->h_union.dev + (size_t)e * 4 * ctx->union_cap(), ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->union_ev[e], ctx->stream));
-    ctx->union_seq[e] = seq;
+    ctx->union_seq[e] = src.key;
     ctx->union_src[e] = src;
     ctx->union_nobj[e] = nobj;
     ctx->union_gen[e] = ctx->scene_gen;
     return ERAY_OK;
 }
+}  // namespace
 
 extern "C" {
 
@@ -1568,12 +1552,7 @@ int eray_render_prepare_ring(eray_ctx* ctx, const eray_render_params* rp, const 
     Ring r;
     if (int st = make_ring(ctx, rp, p, ring, &r)) return st;
     Plan plan;
-    auto body = [&](uint32_t f, uint32_t n) -> int {
-        if (f % r.per_launch) return ERAY_OK;  // rendered by the launch of frame f - f % per_launch
-        HIP_TRY(ctx, launch_frame(ctx, ring_frames(p, r, f, std::min(r.per_launch, n - f))));
-        return ERAY_OK;
-    };
-    return ensure_plan(ctx, ring_key(params_key(p, 0), r), frames, body, &plan);
+    return StaticRing{ctx, p, r, frames}.plan(&plan);
 }
 
 uint32_t eray_frames_per_launch(eray_ctx* ctx, const eray_render_params* rp, uint32_t slots) {
@@ -1581,7 +1560,7 @@ uint32_t eray_frames_per_launch(eray_ctx* ctx, const eray_render_params* rp, uin
     if (rp->anti_aliasing || rp->bounces) return 1u;
     uint32_t W, H;
     eray_camera_size(&ctx->camera, &W, &H);
-    bool binned = false;
+    bool binned = false;  // (from the objects: the scene may not be synchronised yet, ctx->binned)
     for (auto& o : ctx->objects) binned |= o.T > kDirectMax;
     return auto_frames(W, rp->rows, slots, binned);
 }
@@ -1599,16 +1578,10 @@ int eray_render_frames_ring(eray_ctx* ctx, const eray_render_params* rp, const e
     if (empty || !frames) return ERAY_OK;
     Ring r;
     if (int st = make_ring(ctx, rp, p, ring, &r)) return st;
+    const StaticRing run{ctx, p, r, frames};
     Plan plan;
-    auto body = [&](uint32_t f, uint32_t n) -> int {
-        if (f % r.per_launch) return ERAY_OK;
-        HIP_TRY(ctx, launch_frame(ctx, ring_frames(p, r, f, std::min(r.per_launch, n - f))));
-        return ERAY_OK;
-    };
-    if (int st = ensure_plan(ctx, ring_key(params_key(p, 0), r), frames, body, &plan)) return st;
-    auto none = [](uint32_t, uint32_t) { return (int)ERAY_OK; };
-    auto plain = [&](uint32_t f) { return body(f, frames); };
-    const int st = replay(ctx, plan, frames, none, plain, mean_frame_ms);
+    if (int st = run.plan(&plan)) return st;
+    const int st = timed_frames(ctx, frames, mean_frame_ms, [&] { return replay(ctx, plan, frames, run); });
     if (!st) tag_frames(ctx, p.out_ppm, r.ppm, std::min(frames, r.slots), render_source(ctx, p, rp));
     return st;
 }
@@ -1630,63 +1603,41 @@ int eray_time_frames_ring(eray_ctx* ctx, const eray_render_params* rp, const era
     Ring r;
     if (int st = make_ring(ctx, rp, p, ring, &r)) return st;
     const uint32_t F = r.per_launch, L = std::max(1u, frames / F);
-    std::vector<hipEvent_t> ev(4 * (size_t)L, nullptr);
-    auto drop = [&]() {
-        for (auto e : ev)
-            if (e) hipEventDestroy(e);
-    };
-    int st = ERAY_OK;
+    LaunchTimers t(L, 4);  // per launch: the frame kernel's pair, the separate fill's pair
+    HIP_TRY(ctx, t.create());
     std::vector<uint32_t> fill_used(L, 0u);
-    for (uint32_t l = 0; l < L && !st; ++l) {
+    for (uint32_t l = 0; l < L; ++l) {
         LaunchCtx lc = ctx->lc;
-        for (int k = 0; k < 4 && !st; ++k) {
-            const hipError_t e = hipEventCreate(&ev[4 * (size_t)l + k]);
-            if (e != hipSuccess) st = set_error(ctx, ERAY_E_HIP, "hipEventCreate: %s", hipGetErrorString(e));
-        }
-        if (st) break;
-        lc.frame_t[0] = ev[4 * (size_t)l];
-        lc.frame_t[1] = ev[4 * (size_t)l + 1];
-        lc.fill_t[0] = ev[4 * (size_t)l + 2];
-        lc.fill_t[1] = ev[4 * (size_t)l + 3];
+        lc.frame_t[0] = t.at(l, 0);
+        lc.frame_t[1] = t.at(l, 1);
+        lc.fill_t[0] = t.at(l, 2);
+        lc.fill_t[1] = t.at(l, 3);
         lc.fill_used = &fill_used[l];
-        const hipError_t e = launch_render(ring_frames(p, r, l * F, F), lc, ctx->stream);
-        if (e != hipSuccess) st = set_error(ctx, ERAY_E_HIP, "timed frame launch: %s", hipGetErrorString(e));
+        HIP_TRY(ctx, launch_render(ring_frames(p, r, l * F, F), lc, ctx->stream));
     }
-    hipError_t e = st ? hipSuccess : hipStreamSynchronize(ctx->stream);
-    double sum = 0.0, fill = 0.0, span = 0.0;
-    float lo = 0.0f, hi = 0.0f;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    eray_kernel_times res{};
+    HIP_TRY(ctx, t.reduce(F, &res));
+    double fill = 0.0, span = 0.0;
     uint32_t nfill = 0;
-    for (uint32_t l = 0; l < L && !st && e == hipSuccess; ++l) {
-        hipEvent_t* q = &ev[4 * (size_t)l];
-        float k = 0.0f;
-        if ((e = hipEventElapsedTime(&k, q[0], q[1])) != hipSuccess) break;
-        sum += k;
-        lo = l ? std::min(lo, k) : k;
-        hi = l ? std::max(hi, k) : k;
-        float s = k;
+    for (uint32_t l = 0; l < L; ++l) {
+        float s = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&s, t.at(l, 0), t.at(l, 1)));
         if (fill_used[l]) {  // the separate fill beside it: both kernels' span, from the frame kernel's start
             float f0 = 0.0f, f1 = 0.0f, fk = 0.0f;
-            if ((e = hipEventElapsedTime(&fk, q[2], q[3])) != hipSuccess ||
-                (e = hipEventElapsedTime(&f0, q[0], q[2])) != hipSuccess ||
-                (e = hipEventElapsedTime(&f1, q[0], q[3])) != hipSuccess)
-                break;
+            HIP_TRY(ctx, hipEventElapsedTime(&fk, t.at(l, 2), t.at(l, 3)));
+            HIP_TRY(ctx, hipEventElapsedTime(&f0, t.at(l, 0), t.at(l, 2)));
+            HIP_TRY(ctx, hipEventElapsedTime(&f1, t.at(l, 0), t.at(l, 3)));
             fill += fk;
             ++nfill;
-            s = std::max(k, f1) - std::min(0.0f, f0);
+            s = std::max(s, f1) - std::min(0.0f, f0);
         }
         span += s;
     }
-    drop();
-    if (st) return st;
-    if (e != hipSuccess) return set_error(ctx, ERAY_E_HIP, "kernel timing: %s", hipGetErrorString(e));
     tag_frames(ctx, p.out_ppm, r.ppm, std::min(L * F, r.slots), render_source(ctx, p, rp));
-    out->launches = L;
-    out->frames_per_launch = F;
-    out->frame_kernel_ms = (float)(sum / L);
-    out->frame_kernel_min_ms = lo;
-    out->frame_kernel_max_ms = hi;
-    out->fill_kernel_ms = nfill ? (float)(fill / nfill) : 0.0f;
-    out->launch_span_ms = (float)(span / L);
+    res.fill_kernel_ms = nfill ? (float)(fill / nfill) : 0.0f;
+    res.launch_span_ms = (float)(span / L);
+    *out = res;
     return ERAY_OK;
 }
 
@@ -1706,167 +1657,133 @@ int eray_time_write_ceiling(eray_ctx* ctx, const eray_render_params* rp, const e
     Ring r;
     if (int st = make_ring(ctx, rp, p, ring, &r)) return st;
     const uint32_t F = r.per_launch, L = std::max(1u, frames / F);
-    std::vector<hipEvent_t> ev(2 * (size_t)L, nullptr);
-    int st = ERAY_OK;
-    hipError_t e = hipSuccess;
-    for (size_t k = 0; k < ev.size() && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
-    for (uint32_t l = 0; l < L && e == hipSuccess; ++l) {
-        const hipEvent_t t[2] = {ev[2 * (size_t)l], ev[2 * (size_t)l + 1]};
-        e = launch_write_ceiling(ring_frames(p, r, l * F, F), wgs_per_cu, t, ctx->stream);
+    LaunchTimers t(L, 2);
+    HIP_TRY(ctx, t.create());
+    for (uint32_t l = 0; l < L; ++l) {
+        const hipEvent_t pair[2] = {t.at(l, 0), t.at(l, 1)};
+        HIP_TRY(ctx, launch_write_ceiling(ring_frames(p, r, l * F, F), wgs_per_cu, pair, ctx->stream));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    double sum = 0.0;
-    float lo = 0.0f, hi = 0.0f;
-    for (uint32_t l = 0; l < L && e == hipSuccess; ++l) {
-        float k = 0.0f;
-        if ((e = hipEventElapsedTime(&k, ev[2 * (size_t)l], ev[2 * (size_t)l + 1])) != hipSuccess) break;
-        sum += k;
-        lo = l ? std::min(lo, k) : k;
-        hi = l ? std::max(hi, k) : k;
-    }
-    for (auto x : ev)
-        if (x) hipEventDestroy(x);
-    if (e != hipSuccess) st = set_error(ctx, ERAY_E_HIP, "write ceiling: %s", hipGetErrorString(e));
-    if (st) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    eray_kernel_times res{};
+    HIP_TRY(ctx, t.reduce(F, &res));
     // the slots now hold background frames, not renders of the scene
     tag_frames(ctx, p.out_ppm, r.ppm, std::min(L * F, r.slots), FrameSource{kSrcOther});
-    out->launches = L;
-    out->frames_per_launch = F;
-    out->frame_kernel_ms = (float)(sum / L);
-    out->frame_kernel_min_ms = lo;
-    out->frame_kernel_max_ms = hi;
-    out->launch_span_ms = out->frame_kernel_ms;
+    res.launch_span_ms = res.frame_kernel_ms;
+    *out = res;
     return ERAY_OK;
 }
 
-int eray_render_camera_path_ring(eray_ctx* ctx, const eray_render_params* rp, const eray_frame_ring* ring,
-                                 const eray_camera* cameras, uint32_t n, float* mean_frame_ms) {
-    if (int st = use_device(ctx)) return st;
-    if (mean_frame_ms) *mean_frame_ms = 0.0f;
-    if (!rp) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "params is null");
-    if (n && !cameras) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "cameras is null");
-    uint32_t W, H;
-    eray_camera_size(&ctx->camera, &W, &H);
-    for (uint32_t f = 0; f < n; ++f) {  // one engine image: every camera has the scene camera's size
-        uint32_t w, h;
-        eray_camera_size(&cameras[f], &w, &h);
-        if (w != W || h != H)
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "camera %u: size %ux%u differs from the scene camera's %ux%u",
-                             f, w, h, W, H);
-    }
-    FrameParams p;
-    bool empty = false;
-    // the scene camera's setup (scene upload, bins layout; the last known detail count steers the
-    // launch shape) — enqueued, not waited for: the path's frames read their own cameras' setups
-    if (int st = prepare_render(ctx, rp, &p, &empty, SetupWait::kNo)) return st;
-    if (empty || !n) return ERAY_OK;
-    Ring r;
-    if (int st = make_ring(ctx, rp, p, ring, &r)) return st;
-    if (!p.cull) {  // anti-aliasing, bounces, brute force: no per-camera setup, camera in the arguments
-        const eray_camera saved = ctx->camera;
-        hipEvent_t ev[2] = {nullptr, nullptr};  // mean device ms per frame, as replay() times it
-        if (mean_frame_ms) {
-            for (auto& e : ev) HIP_TRY(ctx, hipEventCreate(&e));
-            HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-        }
-        auto drop = [&]() {
-            for (auto e : ev)
-                if (e) hipEventDestroy(e);
-        };
+}  // extern "C"
+
+namespace {
+// ---- camera paths (eray_render_camera_path_ring): one frame per camera
+//
+// Anti-aliasing, bounces, brute force: no per-camera setup — every frame is prepared with its
+// camera as the context's (camera in the kernel arguments) and launched plainly.
+int general_path(eray_ctx* ctx, const eray_render_params* rp, const FrameParams& p, const Ring& r,
+                 const eray_camera* cameras, uint32_t n, float* mean_ms) {
+    const eray_camera saved = ctx->camera;
+    const int st = timed_frames(ctx, n, mean_ms, [&]() -> int {
         for (uint32_t f = 0; f < n; ++f) {
             ctx->camera = cameras[f];
             FrameParams q;
-            int st = prepare_render(ctx, rp, &q, &empty);
-            if (!st && !empty) {
-                const hipError_t e = launch_frame(ctx, ring_frames(q, r, f, 1));
-                if (e != hipSuccess) st = set_error(ctx, ERAY_E_HIP, "render: %s", hipGetErrorString(e));
-            }
-            if (st) {
-                ctx->camera = saved;
-                drop();
-                return st;
-            }
-        }
-        ctx->camera = saved;
-        FrameSource other;
-        other.kind = kSrcOther;
-        tag_frames(ctx, p.out_ppm, r.ppm, std::min(n, r.slots), other);
-        if (mean_frame_ms) {
-            hipError_t e = hipEventRecord(ev[1], ctx->stream);
-            float ms = 0.0f;
-            if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-            drop();
-            if (e != hipSuccess) return set_error(ctx, ERAY_E_HIP, "camera path timing: %s", hipGetErrorString(e));
-            *mean_frame_ms = ms / (float)n;
+            bool empty = false;
+            if (int st = prepare_render(ctx, rp, &q, &empty)) return st;
+            if (!empty) HIP_TRY(ctx, launch_frame(ctx, ring_frames(q, r, f, 1)));
         }
         return ERAY_OK;
-    }
-    // device-camera mode: every frame reads its setup's CamState; the per-frame detail lists are
-    // appended split (heavy sub-blocks from the front, light ones from the back: CamState counts)
-    p.cam_state = ctx->d_state;
-    p.detail_heavy = nullptr;
-    p.dlist_split = p.detail_list ? (uint32_t)ctx->bins.nsub : 0u;
-    p.nrect = 0;
-    std::memset(p.rects, 0, sizeof p.rects);
-    // the cameras: staged in pinned memory, copied to the device once per call; each graph chunk
-    // reads its cameras from d_path (a device-to-device copy of its slice before each replay)
+    });
+    ctx->camera = saved;
+    if (!st) tag_frames(ctx, p.out_ppm, r.ppm, std::min(n, r.slots), FrameSource{kSrcOther});
+    return st;
+}
+
+// The path's cameras to the device: staged in pinned memory and copied once per call, the whole
+// path to d_path_all — each graph chunk reads its cameras from d_path (a device-to-device copy of
+// its slice before each replay, PathCall::before_chunk) — or, a path of one graph chunk, straight
+// into the chunk's camera slots (no per-chunk copy).
+int stage_path_cameras(eray_ctx* ctx, const eray_camera* cameras, uint32_t n) {
     const uint32_t hb = ctx->path_buf;
     ctx->path_buf ^= 1u;
-    CamDev*& h_path = ctx->h_path[hb];
-    if (ctx->h_path_cap[hb] < n) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->path_ev[hb]));
-        if (h_path) HIP_TRY(ctx, hipHostFree(h_path));
-        h_path = nullptr;
-        HIP_TRY(ctx, hipHostMalloc((void**)&h_path, sizeof(CamDev) * n, hipHostMallocDefault));
-        ctx->h_path_cap[hb] = n;
-    }
+    PinnedBuf<CamDev>& h_path = ctx->h_path[hb];
     HIP_TRY(ctx, hipEventSynchronize(ctx->path_ev[hb]));  // the upload two calls back has read this buffer
+    if (h_path.cap < n) HIP_TRY(ctx, h_path.alloc(n));
     for (uint32_t f = 0; f < n; ++f) h_path[f] = cam_dev(cameras[f]);
-    if (int st = ensure(ctx, &ctx->d_path_all, &ctx->path_all_cap, n)) return st;
-    if (int st = ensure(ctx, &ctx->d_path, &ctx->path_cap, kGraphFrames)) return st;
-    // a path of one graph chunk goes straight into the chunk's camera slots (no per-chunk copy)
-    const bool one_chunk = n <= kGraphFrames;
-    HIP_TRY(ctx, hipMemcpyAsync(one_chunk ? ctx->d_path : ctx->d_path_all, h_path, sizeof(CamDev) * n,
+    if (int st = ctx->d_path_all.ensure(ctx, n)) return st;
+    if (int st = ctx->d_path.ensure(ctx, kGraphFrames)) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(n <= kGraphFrames ? ctx->d_path : ctx->d_path_all, h_path, sizeof(CamDev) * n,
                                 hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->path_ev[hb], ctx->stream));
-    const bool batched = batch_setup_ok(ctx);
-    // scenes with binned objects: the setups of up to mc_k cameras at once (one chain of
-    // kernels for all of them, ensure_multi), then their frames, each from its camera's slices
-    const bool multi = !batched && binned_objects(ctx) > 0;
-    const RowSpan rs = row_span(rp);
-    if (multi)
-        if (int st = ensure_multi(ctx, W, H, rs)) return st;
-    if (multi) {  // frames in flight within one multi-camera build: per_launch divides mc_k
-        while (ctx->mc_k % r.per_launch) r.per_launch /= 2;
-    } else if (!batched) {
-        r.per_launch = 1;  // a setup (screen bins) per frame: one frame per launch
+    return ERAY_OK;
+}
+
+// What the culled path strategies share: the call's frame parameters in device-camera mode (every
+// frame reads its setup's CamState), its ring, rows and staged cameras.  A strategy adds
+// prepare(plan) — its buffers and launch plan — and what replay() asks of a run; in body and
+// plain, `f` is the frame's index in the call (its ring slot).
+struct PathCall {
+    eray_ctx* ctx;
+    FrameParams p;
+    Ring r;
+    uint32_t W, H, n;  // Camera::size, cameras
+    RowSpan rs;
+    uint32_t T, nobj;
+
+    PathCall(eray_ctx* ctx, const eray_render_params* rp, const FrameParams& scene, const Ring& r, uint32_t n)
+        : ctx(ctx), p(scene), r(r), W(scene.cam_w), H(scene.cam_h), n(n), rs(row_span(rp)), T(ctx->total_tris),
+          nobj((uint32_t)ctx->objects.size()) {
+        // the per-frame detail lists are appended split (heavy sub-blocks from the front, light
+        // ones from the back: CamState counts)
+        p.cam_state = ctx->d_state;
+        p.detail_heavy = nullptr;
+        p.dlist_split = p.detail_list ? (uint32_t)ctx->bins.nsub : 0u;
+        p.nrect = 0;
+        std::memset(p.rects, 0, sizeof p.rects);
     }
-    const uint32_t T = ctx->total_tris, nobj = (uint32_t)ctx->objects.size();
-    // this call's frames are camera-path frames (eray_gather_frames): every camera's object
-    // rectangles fold into the union of the call
-    FrameSource psrc;
-    psrc.kind = kSrcPath;
-    psrc.key = ++ctx->path_seq;
-    psrc.W = W;
-    psrc.H = H;
-    psrc.row0 = rs.row0;
-    psrc.rows = rs.rows;
-    psrc.band_shift = rs.band_shift;
-    psrc.band_stride = rs.band_stride;
-    if (int st = ensure_union(ctx, nobj)) return st;
-    if (batched) {
-        if (int st = ensure(ctx, &ctx->d_bcull, &ctx->bcull_cap, (size_t)kGraphFrames * T)) return st;
-        if (int st = ensure(ctx, &ctx->d_bobjs, &ctx->bobjs_cap, (size_t)kGraphFrames * nobj)) return st;
-        if (int st = ensure(ctx, &ctx->d_bstate, &ctx->bstate_cap, kGraphFrames)) return st;
+    // the call's rectangle union is flushed after the timed stretch, and the context's setup is
+    // still the scene camera's afterwards (per-camera slots), unless a strategy says otherwise
+    static constexpr bool kUnionTimed = false;
+    void finish() const {}
+    bool one_chunk() const { return n <= kGraphFrames; }
+    // frame f's camera outside a chunk (plain launches)
+    const CamDev* camera(uint32_t f) const { return (one_chunk() ? ctx->d_path : ctx->d_path_all) + f; }
+    int before_chunk(uint32_t first, uint32_t count) const {
+        if (one_chunk()) return ERAY_OK;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path, ctx->d_path_all + first, sizeof(CamDev) * count,
+                                    hipMemcpyDeviceToDevice, ctx->stream));
+        return ERAY_OK;
     }
-    // frame `slot` of a batch whose setups started at camera `cams` (count cameras) — the batch
-    // is enqueued with its first frame; frames in flight: the launch of slot s (s % per_launch ==
-    // 0) renders slots [s, s + per_launch) of the batch, each from its own setup slot; `f` is the
-    // frame's index in the call (its ring slot)
-    auto batch_frame = [&](const CamDev* cams, uint32_t slot, uint32_t count, uint32_t f) -> int {
+    // The graphs of `run` (kind: batched 2, else 1), keyed with every buffer their kernels hold.
+    template <typename Run>
+    int graph_plan(const Run& run, uint32_t kind, Plan* plan) const {
+        std::vector<unsigned char> key = ring_key(params_key(p, kind), r);
+        for (const void* ptr : {(const void*)ctx->d_path, (const void*)ctx->d_bcull, (const void*)ctx->d_bobjs,
+                                (const void*)ctx->d_bstate, (const void*)ctx->d_union_acc})
+            append(key, ptr);
+        // the captured setup and bins kernels hold every bin buffer's address: a reallocation (a grown
+        // capacity) must never replay a graph of the old buffers, even if some addresses recur
+        append(key, ctx->bins_gen);
+        append(key, (uint64_t)0);  // (the multi-camera buffers' generation, when those were captured)
+        return ensure_plan(ctx, key, n, [&run](uint32_t f, uint32_t count) { return run.body(0, f, count); }, plan);
+    }
+};
+
+// Scenes without binned objects, small enough (batch_setup_ok): a chunk's setups in one launch,
+// enqueued with the chunk's first frame, into per-camera slots; frames in flight.
+struct BatchedPath : PathCall {
+    using PathCall::PathCall;
+    int prepare(Plan* plan) {
+        if (int st = ctx->d_bcull.ensure(ctx, (size_t)kGraphFrames * T)) return st;
+        if (int st = ctx->d_bobjs.ensure(ctx, (size_t)kGraphFrames * nobj)) return st;
+        if (int st = ctx->d_bstate.ensure(ctx, kGraphFrames)) return st;
+        return graph_plan(*this, 2, plan);
+    }
+    // frame `slot` of a batch whose setups started at camera `cams` (count cameras): the launch of
+    // slot s (s % per_launch == 0) renders slots [s, s + per_launch) of the batch, each from its
+    // own setup slot
+    int frame(const CamDev* cams, uint32_t slot, uint32_t count, uint32_t f, uint32_t per_launch) const {
         if (slot == 0) {
-            SetupParams sp = setup_params(ctx, cams, W, H, row_span(rp));
+            SetupParams sp = setup_params(ctx, cams, W, H, rs);
             sp.cull = ctx->d_bcull;
             sp.objs = ctx->d_bobjs;
             sp.objs_src = ctx->d_objs;
@@ -1875,22 +1792,41 @@ int eray_render_camera_path_ring(eray_ctx* ctx, const eray_render_params* rp, co
             sp.union_nobj = nobj;
             HIP_TRY(ctx, launch_camera_setup_batch(sp, count, ctx->stream));
         }
-        if (slot % r.per_launch) return ERAY_OK;
-        FrameParams q = ring_frames(p, r, f, std::min(r.per_launch, count - slot));
+        if (slot % per_launch) return ERAY_OK;
+        FrameParams q = ring_frames(p, r, f, std::min(per_launch, count - slot));
         q.cam_state = ctx->d_bstate + slot;
         q.cull = ctx->d_bcull + (size_t)slot * T;
         q.objects = ctx->d_bobjs + (size_t)slot * nobj;
         q.dev_slots = 1;
         HIP_TRY(ctx, launch_frame(ctx, q));
         return ERAY_OK;
-    };
-    // frame `slot` of a run of `count` cameras at `cams` (f: its index in the call, its ring slot):
-    // batch b = slot / K of the run is built into set b % 2; the first batch's build on the main
-    // stream, every later one on mc_stream while the previous batch's frames render (it waits for
-    // the frames of batch b - 2, the set's previous users), the frames wait for their build;
-    // frames in flight: the launch of slot s (s % per_launch == 0) renders slots [s, s + n) of
-    // the batch (per_launch divides K, so a launch never spans two builds), each from its slices
-    auto multi_frame = [&](const CamDev* cams, uint32_t slot, uint32_t count, uint32_t f) -> int {
+    }
+    int body(uint32_t first, uint32_t f, uint32_t count) const { return frame(ctx->d_path, f, count, first + f, r.per_launch); }
+    int plain(uint32_t f) const { return frame(camera(f), 0, 1, f, 1); }  // a batch of one
+};
+
+// Scenes with binned objects: the setups of up to mc_k cameras at once (one chain of kernels for
+// all of them, ensure_multi), then their frames, each from its camera's slices.
+// Multi-camera builds on two streams: enqueued directly, chunk by chunk, not replayed from a
+// captured graph (the graph executor left the GPU idle for milliseconds after a path's first
+// builds; same-box A/B, scripts/ab_multi.sh: C5's frame 475-485 -> 468 us, 3840x2160 / 70k
+// 88-91 -> 57-58 us per moving frame)
+struct MultiPath : PathCall {
+    static constexpr bool kUnionTimed = true;  // (the union's flush is enqueued inside the timed stretch)
+    using PathCall::PathCall;
+    int prepare(Plan* plan) {
+        if (int st = ensure_multi(ctx, W, H, rs)) return st;
+        while (ctx->mc_k % r.per_launch) r.per_launch /= 2;  // frames in flight within one build: per_launch divides mc_k
+        *plan = direct_plan(n);
+        return ERAY_OK;
+    }
+    // frame `slot` of a run of `count` cameras at `cams`: batch b = slot / K of the run is built
+    // into set b % 2; the first batch's build on the main stream, every later one on mc_stream
+    // while the previous batch's frames render (it waits for the frames of batch b - 2, the set's
+    // previous users), the frames wait for their build; frames in flight: the launch of slot s
+    // (s % per_launch == 0) renders slots [s, s + n) of the batch (per_launch divides K, so a
+    // launch never spans two builds), each from its slices
+    int frame(const CamDev* cams, uint32_t slot, uint32_t count, uint32_t f) const {
         const uint32_t K = ctx->mc_k, k = slot % K, b = slot / K;
         auto& m = ctx->mc[b & 1u];
         if (k == 0) {
@@ -1924,85 +1860,85 @@ int eray_render_camera_path_ring(eray_ctx* ctx, const eray_render_params* rp, co
         HIP_TRY(ctx, launch_frame(ctx, q));
         if (k + nf >= K || slot + nf >= count) HIP_TRY(ctx, hipEventRecord(ctx->mc_free[b & 1u], ctx->stream));
         return ERAY_OK;
-    };
-    auto frame = [&](const CamDev* cam, uint32_t f) -> int {
-        if (multi) return multi_frame(cam, 0, 1, f);
-        if (batched) {
-            const Ring keep = r;
-            r.per_launch = 1;
-            const int st = batch_frame(cam, 0, 1, f);
-            r = keep;
-            return st;
-        }
-        if (int st = enqueue_setup(ctx, cam, W, H, row_span(rp), false, false, ctx->d_union_acc)) return st;
+    }
+    int body(uint32_t first, uint32_t f, uint32_t count) const { return frame(ctx->d_path, f, count, first + f); }
+    int plain(uint32_t f) const { return frame(camera(f), 0, 1, f); }
+};
+
+// Any other scene: the context's own setup (screen bins) and one frame per camera.
+struct PerFramePath : PathCall {
+    using PathCall::PathCall;
+    int prepare(Plan* plan) {
+        r.per_launch = 1;
+        return graph_plan(*this, 1, plan);
+    }
+    int frame(const CamDev* cam, uint32_t f) const {
+        if (int st = enqueue_setup(ctx, cam, W, H, rs, false, false, ctx->d_union_acc)) return st;
         HIP_TRY(ctx, launch_frame(ctx, ring_frames(p, r, f, 1)));
         return ERAY_OK;
-    };
-    auto body = [&](uint32_t f, uint32_t count) {
-        if (multi) return multi_frame(ctx->d_path, f, count, f);
-        return batched ? batch_frame(ctx->d_path, f, count, f) : frame(ctx->d_path + f, f);
-    };
-    std::vector<unsigned char> key = ring_key(params_key(p, batched ? 2 : 1), r);
-    for (const void* ptr : {(const void*)ctx->d_path, (const void*)ctx->d_bcull, (const void*)ctx->d_bobjs,
-                            (const void*)ctx->d_bstate, (const void*)ctx->d_union_acc})
-        key.insert(key.end(), reinterpret_cast<const unsigned char*>(&ptr),
-                   reinterpret_cast<const unsigned char*>(&ptr) + sizeof ptr);
-    // the captured setup and bins kernels hold every bin buffer's address: a reallocation (a grown
-    // capacity) must never replay a graph of the old buffers, even if some addresses recur
-    key.insert(key.end(), reinterpret_cast<const unsigned char*>(&ctx->bins_gen),
-               reinterpret_cast<const unsigned char*>(&ctx->bins_gen) + sizeof ctx->bins_gen);
-    const uint64_t mc_gen = multi ? ctx->mc_gen : 0u;  // (likewise the multi-camera buffers)
-    key.insert(key.end(), reinterpret_cast<const unsigned char*>(&mc_gen),
-               reinterpret_cast<const unsigned char*>(&mc_gen) + sizeof mc_gen);
-    auto before = [&](uint32_t first, uint32_t count) -> int {
-        if (one_chunk) return ERAY_OK;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_path, ctx->d_path_all + first, sizeof(CamDev) * count,
-                                    hipMemcpyDeviceToDevice, ctx->stream));
-        return ERAY_OK;
-    };
-    // multi-camera builds on two streams: enqueued directly, chunk by chunk, not replayed from a
-    // captured graph (the graph executor left the GPU idle for milliseconds after a path's first
-    // builds; same-box A/B, scripts/ab_multi.sh: C5's frame 475-485 -> 468 us, 3840x2160 / 70k
-    // 88-91 -> 57-58 us per moving frame)
-    if (multi) {
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        if (mean_frame_ms) {
-            for (auto& e : ev) HIP_TRY(ctx, hipEventCreate(&e));
-            HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
-        }
-        int st = ERAY_OK;
-        for (uint32_t first = 0; first < n && !st; first += kGraphFrames) {
-            const uint32_t count = std::min(kGraphFrames, n - first);
-            st = before(first, count);
-            for (uint32_t f = 0; f < count && !st; ++f) st = multi_frame(ctx->d_path, f, count, first + f);
-        }
-        if (!st) st = finish_union(ctx, psrc.key, psrc, nobj);
-        if (!st) tag_frames(ctx, p.out_ppm, r.ppm, std::min(n, r.slots), psrc);
-        if (mean_frame_ms && !st) {
-            float ms = 0.0f;
-            hipError_t e = hipEventRecord(ev[1], ctx->stream);
-            if (e == hipSuccess) e = hipEventSynchronize(ev[1]);
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-            if (e != hipSuccess) st = set_error(ctx, ERAY_E_HIP, "camera path timing: %s", hipGetErrorString(e));
-            else *mean_frame_ms = ms / (float)n;
-        }
-        for (auto e : ev)
-            if (e) hipEventDestroy(e);
-        return st;
     }
-    Plan plan;
-    if (int st = ensure_plan(ctx, key, n, body, &plan)) return st;
-    auto plain = [&](uint32_t f) { return frame((one_chunk ? ctx->d_path : ctx->d_path_all) + f, f); };
-    int st = replay(ctx, plan, n, before, plain, mean_frame_ms);
-    if (!st) st = finish_union(ctx, psrc.key, psrc, nobj);
-    if (!st) tag_frames(ctx, p.out_ppm, r.ppm, std::min(n, r.slots), psrc);
-    if (batched || multi) return st;  // (per-camera slots: the context's setup is still the scene camera's)
+    int body(uint32_t first, uint32_t f, uint32_t) const { return frame(ctx->d_path + f, first + f); }
+    int plain(uint32_t f) const { return frame(camera(f), f); }
     // the device state now belongs to the path's last camera: the scene camera is set up again at
     // its next render (whose count copy also grows the bins' capacity when a camera needed more;
     // no copy here: waiting for an earlier one would wait for that call's frames)
-    ctx->setup_key.clear();
-    ctx->state_known = false;
+    void finish() const {
+        ctx->setup_key.clear();
+        ctx->state_known = false;
+    }
+};
+
+// Runs a path strategy: its plan, the frames (timed when asked), the call's rectangle union and
+// the frames' tags.  This call's frames are camera-path frames (eray_gather_frames): every
+// camera's object rectangles fold into the union of the call.
+template <typename Strategy>
+int run_path(Strategy s, float* mean_ms) {
+    eray_ctx* ctx = s.ctx;
+    if (int st = ensure_union(ctx, s.nobj)) return st;
+    Plan plan;
+    if (int st = s.prepare(&plan)) return st;
+    const FrameSource src = frame_source(kSrcPath, ++ctx->path_seq, s.W, s.H, s.rs);
+    int st = timed_frames(ctx, s.n, mean_ms, [&]() -> int {
+        const int st = replay(ctx, plan, s.n, s);
+        return st || !Strategy::kUnionTimed ? st : finish_union(ctx, src, s.nobj);
+    });
+    if (!st && !Strategy::kUnionTimed) st = finish_union(ctx, src, s.nobj);
+    if (!st) tag_frames(ctx, s.p.out_ppm, s.r.ppm, std::min(s.n, s.r.slots), src);
+    s.finish();
     return st;
+}
+}  // namespace
+
+extern "C" {
+
+int eray_render_camera_path_ring(eray_ctx* ctx, const eray_render_params* rp, const eray_frame_ring* ring,
+                                 const eray_camera* cameras, uint32_t n, float* mean_frame_ms) {
+    if (int st = use_device(ctx)) return st;
+    if (mean_frame_ms) *mean_frame_ms = 0.0f;
+    if (!rp) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "params is null");
+    if (n && !cameras) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "cameras is null");
+    uint32_t W, H;
+    eray_camera_size(&ctx->camera, &W, &H);
+    for (uint32_t f = 0; f < n; ++f) {  // one engine image: every camera has the scene camera's size
+        uint32_t w, h;
+        eray_camera_size(&cameras[f], &w, &h);
+        if (w != W || h != H)
+            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "camera %u: size %ux%u differs from the scene camera's %ux%u",
+                             f, w, h, W, H);
+    }
+    FrameParams p;
+    bool empty = false;
+    // the scene camera's setup (scene upload, bins layout; the last known detail count steers the
+    // launch shape) — enqueued, not waited for: the path's frames read their own cameras' setups
+    if (int st = prepare_render(ctx, rp, &p, &empty, SetupWait::kNo)) return st;
+    if (empty || !n) return ERAY_OK;
+    Ring r;
+    if (int st = make_ring(ctx, rp, p, ring, &r)) return st;
+    if (!p.cull) return general_path(ctx, rp, p, r, cameras, n, mean_frame_ms);
+    if (int st = stage_path_cameras(ctx, cameras, n)) return st;
+    if (batch_setup_ok(ctx)) return run_path(BatchedPath(ctx, rp, p, r, n), mean_frame_ms);
+    if (ctx->binned) return run_path(MultiPath(ctx, rp, p, r, n), mean_frame_ms);
+    return run_path(PerFramePath(ctx, rp, p, r, n), mean_frame_ms);
 }
 
 int eray_render_camera_path(eray_ctx* ctx, const eray_render_params* rp, const eray_camera* cameras, uint32_t n,
@@ -2094,11 +2030,11 @@ int eray_internal_source_layout(eray_ctx* ctx, const FrameSource& src, SceneLayo
                              "gather: these camera-path frames are older than the last %u paths", kUnionRing);
         // (the union covers the objects of the scene the path was rendered from; a scene change
         // since makes the path's frames ungatherable, as their objects no longer exist)
-        if (ctx->union_nobj[e] != nobj || ctx->union_gen[e] != ctx->scene_gen || nobj > ctx->union_cap)
+        if (ctx->union_nobj[e] != nobj || ctx->union_gen[e] != ctx->scene_gen || nobj > ctx->union_cap())
             return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
                              "gather: the scene changed after these camera-path frames were rendered");
         HIP_TRY(ctx, hipEventSynchronize(ctx->union_ev[e]));
-        const int32_t* u = ctx->h_union + (size_t)e * 4 * ctx->union_cap;
+        const int32_t* u = ctx->h_union + (size_t)e * 4 * ctx->union_cap();
         for (size_t i = 0; i < nobj; ++i)
             out->rects.push_back({u[2 * i], u[2 * nobj + 2 * i], u[2 * i + 1], u[2 * nobj + 2 * i + 1]});
         return ERAY_OK;
@@ -2130,7 +2066,7 @@ void eray_internal_untag(eray_ctx* ctx, const void* p, size_t bytes) {
 }
 void* eray_internal_staging(eray_ctx* ctx, size_t bytes) {
     if (!ctx) return nullptr;
-    if (ensure(ctx, &ctx->d_staging, &ctx->staging_cap, bytes)) return nullptr;
+    if (ctx->d_staging.ensure(ctx, bytes)) return nullptr;
     return ctx->d_staging;
 }
 

@@ -1,0 +1,124 @@
+// owners.hpp — move-only owners of the HIP resources the C-ABI layer holds (host code only: no
+// kernel sees these types).  Each destructor releases its resource; each converts to the raw
+// handle or pointer it owns, so launch parameters are filled as from raw fields.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+struct eray_ctx;
+
+namespace eray {
+namespace gpu {
+
+// A HIP handle (a pointer type) released by Destroy.
+template <typename H, hipError_t (*Destroy)(H)>
+class Handle {
+public:
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    Handle& operator=(Handle&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = std::exchange(o.h_, nullptr);
+        }
+        return *this;
+    }
+    ~Handle() { reset(); }
+    void reset() {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    operator H() const { return h_; }
+    H* put() {  // for the creating call (releases what it held)
+        reset();
+        return &h_;
+    }
+
+private:
+    H h_ = nullptr;
+};
+
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(put(), flags); }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags) { return hipStreamCreateWithFlags(put(), flags); }
+    hipError_t create(unsigned flags, int priority) { return hipStreamCreateWithPriority(put(), flags, priority); }
+};
+using Graph = Handle<hipGraph_t, hipGraphDestroy>;
+using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
+
+// A captured launch plan with the key it was captured for (capi.cpp ensure_graph).
+struct FrameGraph {
+    Graph graph;
+    GraphExec exec;  // (destroyed before its graph)
+    std::vector<unsigned char> key;
+    uint64_t used = 0;
+};
+
+// `cap` elements of T, released by Free (device or pinned host memory).
+template <typename T, hipError_t (*Free)(void*)>
+class Buffer {
+public:
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    Buffer& operator=(Buffer&& o) noexcept {
+        if (this != &o) {
+            (void)release();
+            p_ = std::exchange(o.p_, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~Buffer() { (void)release(); }
+    hipError_t release() {
+        const hipError_t e = p_ ? Free(p_) : hipSuccess;
+        p_ = nullptr;
+        cap = 0;
+        return e;
+    }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+
+protected:
+    T* p_ = nullptr;
+
+public:
+    size_t cap = 0;  // elements
+};
+
+template <typename T>
+struct DeviceBuf : Buffer<T, hipFree> {
+    hipError_t alloc(size_t n) {  // n >= 1 elements, replacing what it held
+        hipError_t e = this->release();
+        if (e == hipSuccess) e = hipMalloc((void**)&this->p_, n * sizeof(T));
+        if (e == hipSuccess) this->cap = n;
+        return e;
+    }
+    // At least `need` elements: nothing when they fit, else ctx's stream is synchronised, the old
+    // allocation freed and max(need, 1) elements allocated (contents are not kept).  An eray
+    // status; defined in capi.cpp.
+    int ensure(eray_ctx* ctx, size_t need);
+};
+
+// Pinned host memory; allocated with hipHostMallocMapped, `dev` is its device address.
+template <typename T>
+struct PinnedBuf : Buffer<T, hipHostFree> {
+    T* dev = nullptr;
+    hipError_t alloc(size_t n, unsigned flags = hipHostMallocDefault) {
+        dev = nullptr;
+        hipError_t e = this->release();
+        if (e == hipSuccess) e = hipHostMalloc((void**)&this->p_, n * sizeof(T), flags);
+        if (e == hipSuccess) this->cap = n;
+        if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer((void**)&dev, this->p_, 0);
+        return e;
+    }
+};
+
+}  // namespace gpu
+}  // namespace eray

@@ -51,10 +51,10 @@ class Out:
             a.free()
 
 
-def per_camera(ctx, out, cam, flags=0):
+def per_camera(ctx, out, cam, flags=0, **params):
     ctx.set_camera(cam)
     out.clear()
-    ctx.render(out.W, out.H, flags=flags, **out.kw())
+    ctx.render(out.W, out.H, flags=flags, **params, **out.kw())
     return [a.copy() for a in out.get()]
 
 
@@ -245,4 +245,146 @@ def test_path_graph_not_replayed_after_bin_reallocation(gpu, standin70k):
             check(out.get(), ref, f"path after reallocation {rep}")
     finally:
         out.free()
+        sc.close()
+
+
+def test_general_mode_path_equals_per_camera_renders(gpu, oracle, cube):
+    """Brute force and anti-aliasing take the path's general mode (no per-camera setup: every frame
+    is prepared with its camera as the context's): each prefix ends on its last camera's frame as
+    eray_render writes it, and the scene camera is the context's again afterwards."""
+    W, H = 64, 36
+    sc = MainScene(gpu, *cube, W, H, texture=256, fov=(16.0, 9.0))
+    out = Out(gpu, W, H)
+    cams = dolly(3, width=W)
+    home = capi.make_camera((0.0, 0.0, 5.0), (16.0, 9.0), W, 1.0)
+    try:
+        for params in (dict(flags=capi.RENDER_BRUTE_FORCE),
+                       dict(flags=capi.RENDER_BRUTE_FORCE, anti_aliasing=2, aa_seed=0x5EED1234)):
+            refs = [per_camera(gpu, out, c, **params) for c in cams]
+            assert len({r[0].tobytes() for r in refs}) == len(refs)  # the cameras see different frames
+            gpu.set_camera(home)
+            for k in range(len(cams)):
+                out.clear()
+                ms = gpu.render_camera_path(cams[: k + 1], W, H, timed=True, **params, **out.kw())
+                assert ms > 0.0
+                check(out.get(), refs[k], f"general path frame {k} ({params})")
+        out.clear()
+        gpu.render(W, H, **out.kw())  # no set_camera: the path left the scene camera in place
+        got = out.get()
+        ref, ref_face, _ = oracle.render(oracle.main_rs_scene(*cube, texture=256),
+                                         oracle.camera((0.0, 0.0, 5.0), (16.0, 9.0), W, 1.0), want_faces=True)
+        assert np.array_equal(got[1], ref_face)
+        assert_bit_equal(got[0], ref, "scene camera after general paths")
+    finally:
+        out.free()
+        sc.close()
+
+
+def test_path_with_one_setup_per_frame(gpu):
+    """257 objects (one more than the batched setups hold) and none binned: the path enqueues a
+    setup and a frame per camera.  Each prefix ends on the brute-force frame of its last camera."""
+    from tests.helpers import random_mesh
+    rng = np.random.default_rng(33)
+    W, H = 128, 72
+    gpu.scene_reset()
+    gpu.set_camera(capi.make_camera((0.0, 0.0, 4.0), (16.0, 9.0), W, 1.0))
+    keep = []
+    for k in range(257):
+        center = rng.uniform(-1, 1, 3) * (1.6, 0.9, 0.5)
+        pos, nrm, uv = random_mesh(rng, 1, scale=0.6, center=center)
+        lo, hi = pos.reshape(-1, 3).min(0), pos.reshape(-1, 3).max(0)
+        dc = gpu.to_device(rng.uniform(0, 1, (4, 4, 3)).astype(np.float32))
+        keep.append(dc)
+        gpu.add_object(pos, nrm, uv, tuple(lo), tuple(hi), color=dc.image())
+    gpu.add_light(capi.make_light((0.0, 2.0, 0.0), "ambient", (1.0, 1.0, 1.0), 0.2))
+    gpu.add_light(capi.make_light((1.0, 1.0, 2.0), "point", (1.0, 0.8, 0.6), 1.0))
+    out = Out(gpu, W, H)
+    try:
+        cams = orbit(3, width=W)
+        refs = [per_camera(gpu, out, c, flags=capi.RENDER_BRUTE_FORCE) for c in cams]
+        for r in refs:  # not empty frames
+            assert (r[1] >= 0).sum() >= 300
+        assert len({r[1].tobytes() for r in refs}) == 3
+        for k in range(3):
+            out.clear()
+            gpu.render_camera_path(cams[: k + 1], W, H, **out.kw())
+            check(out.get(), refs[k], f"per-frame setup, frame {k}")
+        path = [cams[f % 3] for f in range(66)]  # a chunk graph of 64 and a remainder graph of 2
+        out.clear()
+        gpu.render_camera_path(path, W, H, **out.kw())
+        check(out.get(), refs[65 % 3], "per-frame setup, path of 66")
+    finally:
+        out.free()
+        for a in keep:
+            a.free()
+
+
+def test_path_remainder_of_one_frame_is_a_plain_launch(gpu, cube):
+    """65 frames: a chunk graph of 64 and one frame left over, which no graph covers."""
+    W, H = 320, 180
+    sc = MainScene(gpu, *cube, W, H, texture=256, fov=(16.0, 9.0))
+    out = Out(gpu, W, H)
+    cams = dolly(7, width=W)
+    try:
+        ref = per_camera(gpu, out, cams[64 % 7])
+        gpu.set_camera(capi.make_camera((0.0, 0.0, 5.0), (16.0, 9.0), W, 1.0))
+        out.clear()
+        gpu.render_camera_path([cams[f % 7] for f in range(65)], W, H, **out.kw())
+        check(out.get(), ref, "path of 65")
+    finally:
+        out.free()
+        sc.close()
+
+
+def test_context_lifecycle(gpu, cube):
+    """A second context that has used a static ring, a batched path and a binned (multi-camera)
+    path is closed, twice over; the session's context renders as before."""
+    v, n, t, fv, ft, fn = meshgen.displaced_sphere(600, 5)
+    sphere = (np.ascontiguousarray(v[fv].reshape(-1, 9)), np.ascontiguousarray(n[fn].reshape(-1, 9)),
+              np.ascontiguousarray(t[ft].reshape(-1, 6)))
+    W, H = 96, 54
+    sc = MainScene(gpu, *cube, W, H, texture=64, fov=(16.0, 9.0))
+    mine = Out(gpu, W, H)
+
+    def one_life():
+        with capi.Context(0) as ctx:
+            out = Out(ctx, W, H)
+            rgb = ctx.empty((4, H, W, 3), np.float32)
+            scene = MainScene(ctx, *cube, W, H, texture=64, fov=(16.0, 9.0))
+            cams = dolly(3, width=W)
+            try:
+                refs = [per_camera(ctx, out, c) for c in cams]
+                ctx.render_frames(6, W, H, out_rgb=rgb.ptr, ring=capi.frame_ring(4, H, W))
+                ctx.synchronize()
+                slots = rgb.numpy()
+                for s in range(4):
+                    assert_bit_equal(slots[s], refs[2][0], f"ring slot {s}")
+                out.clear()
+                ctx.render_camera_path(cams, W, H, **out.kw())
+                check(out.get(), refs[2], "batched path")
+                scene.close()
+                scene = MainScene(ctx, *sphere, W, H, texture=64, fov=(16.0, 9.0))
+                cams = dolly(3, width=W, z=4.5, amp=1.2)
+                ref = per_camera(ctx, out, cams[2], flags=capi.RENDER_BRUTE_FORCE)
+                assert (ref[1] >= 0).any()
+                out.clear()
+                ctx.render_camera_path(cams, W, H, **out.kw())
+                check(out.get(), ref, "binned path")
+            finally:
+                scene.close()
+                rgb.free()
+                out.free()
+
+    try:
+        mine.clear()
+        gpu.render(W, H, **mine.kw())
+        before = [a.copy() for a in mine.get()]
+        assert (before[1] >= 0).any()
+        one_life()
+        one_life()
+        mine.clear()
+        gpu.render(W, H, **mine.kw())
+        check(mine.get(), before, "the session's context after two others")
+    finally:
+        mine.free()
         sc.close()
