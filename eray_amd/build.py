@@ -24,7 +24,8 @@ OBJ = os.path.join(PKG, "_obj")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "liberay_hip.so")
 
-SOURCES = ["render.hip", "setup.hip", "trace.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "comm.cpp", "objload.cpp"]
+SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "comm.cpp",
+           "objload.cpp"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
             f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),
@@ -98,7 +99,7 @@ ROCM_LIB = "/opt/rocm/lib"
 
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
-    the eray_main CLI (main.rs) and the tests/cpp/test_host unit-test binary.  Plain g++: the
+    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -131,7 +132,8 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
         run([cxx, "-shared", "-o", HOST_LIB, *objs, *link])
     outs = [HOST_LIB]
     for name, src in (("eray_main", os.path.join(host, "main.cpp")),
-                      ("test_host", os.path.join(ROOT, "tests", "cpp", "test_host.cpp"))):
+                      ("test_host", os.path.join(ROOT, "tests", "cpp", "test_host.cpp")),
+                      ("test_rays", os.path.join(ROOT, "tests", "cpp", "test_rays.cpp"))):
         exe = os.path.join(BIN_DIR, name)
         if force or not _newer(exe, [src, HOST_LIB] + headers):
             run([cxx, *flags, src, "-o", exe, "-L" + LIB_DIR, "-leray_host", *link])

@@ -112,6 +112,30 @@ class RenderParams(C.Structure):
                 ("band_stride", C.c_uint32)]
 
 
+RAYS_NORMALIZE = 1
+RAYS_BRUTE_FORCE = 2
+
+
+class Ray(C.Structure):  # eray_ray
+    _fields_ = [("start", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+class RayHit(C.Structure):  # eray_ray_hit
+    _fields_ = [("object", C.c_int32), ("face", C.c_int32), ("position", C.c_float * 3),
+                ("normal", C.c_float * 3), ("uv", C.c_float * 2), ("u", C.c_float), ("v", C.c_float)]
+
+
+class RaysParams(C.Structure):  # eray_rays_params
+    _fields_ = [("rays", C.c_void_p), ("count", C.c_uint64), ("object", C.c_int32), ("bounces", C.c_uint32),
+                ("flags", C.c_uint32), ("out_hit", C.c_void_p), ("out_rgb", C.c_void_p)]
+
+
+# eray_ray / eray_ray_hit as numpy records
+RAY_DTYPE = np.dtype([("start", np.float32, 3), ("dir", np.float32, 3)])
+HIT_DTYPE = np.dtype([("object", np.int32), ("face", np.int32), ("position", np.float32, 3),
+                      ("normal", np.float32, 3), ("uv", np.float32, 2), ("u", np.float32), ("v", np.float32)])
+
+
 class FrameRing(C.Structure):  # eray_frame_ring
     _fields_ = [("slots", C.c_uint32), ("frames_per_launch", C.c_uint32), ("rgb_stride", C.c_uint64),
                 ("ppm_stride", C.c_uint64), ("face_stride", C.c_uint64)]
@@ -167,6 +191,7 @@ SIGNATURES = {
     "eray_scene_add_object": (C.c_int, [_P, C.POINTER(Object), C.POINTER(_U)]),
     "eray_camera_size": (C.c_int, [C.POINTER(Camera), C.POINTER(_U), C.POINTER(_U)]),
     "eray_render": (C.c_int, [_P, C.POINTER(RenderParams)]),
+    "eray_cast_rays": (C.c_int, [_P, C.POINTER(RaysParams)]),
     "eray_render_frames": (C.c_int, [_P, C.POINTER(RenderParams), _U, C.POINTER(C.c_float)]),
     "eray_render_prepare": (C.c_int, [_P, C.POINTER(RenderParams), _U]),
     "eray_render_camera_path": (C.c_int, [_P, C.POINTER(RenderParams), C.POINTER(Camera), _U,
@@ -551,6 +576,44 @@ class Context:
         p = RenderParams(image_width, image_height, row0, rows, bounces, anti_aliasing,
                          out_rgb or None, out_ppm or None, out_face or None, flags, aa_seed, band_rows, band_stride)
         self._check(lib().eray_render(self._h, C.byref(p)))
+
+    def cast_rays_device(self, rays_ptr, count, out_hit=None, out_rgb=None, object=-1, bounces=0, flags=0) -> None:
+        """eray_cast_rays on device buffers (count eray_ray in, count eray_ray_hit and / or count x 3
+        f32 out): enqueued on the context's stream, nothing copied, nothing waited for."""
+        p = RaysParams(rays_ptr or None, count, object, bounces, flags, out_hit or None, out_rgb or None)
+        self._check(lib().eray_cast_rays(self._h, C.byref(p)))
+
+    def cast_rays(self, rays, object=-1, bounces=0, normalize=False, brute_force=False, want_hits=True,
+                  want_rgb=False):
+        """Object::intersects / Engine::cast_ray for caller-supplied rays (eray_cast_rays).  rays:
+        (n, 6) float32 (start xyz, dir xyz) or RAY_DTYPE records.  Returns the hit records (HIT_DTYPE,
+        object == -1: a miss), the (n, 3) cast_ray sums, or both as a tuple."""
+        r = np.ascontiguousarray(rays)
+        r = (r.view(np.float32) if r.dtype == RAY_DTYPE else r.astype(np.float32, copy=False)).reshape(-1, 6)
+        n = r.shape[0]
+        flags = (RAYS_NORMALIZE if normalize else 0) | (RAYS_BRUTE_FORCE if brute_force else 0)
+        bufs = []
+        try:
+            d_rays = self.to_device(r if n else np.zeros((1, 6), np.float32))
+            bufs.append(d_rays)
+            d_hit = d_rgb = None
+            if want_hits:
+                d_hit = self.empty((max(n, 1),), HIT_DTYPE)
+                bufs.append(d_hit)
+            if want_rgb:
+                d_rgb = self.empty((max(n, 1), 3), np.float32)
+                bufs.append(d_rgb)
+            self.cast_rays_device(d_rays.ptr, n, d_hit.ptr if d_hit else None, d_rgb.ptr if d_rgb else None, object,
+                                  bounces, flags)
+            self.synchronize()
+            hits = d_hit.numpy()[:n] if d_hit else None
+            rgb = d_rgb.numpy()[:n] if d_rgb else None
+        finally:
+            for a in bufs:
+                a.free()
+        if want_hits and want_rgb:
+            return hits, rgb
+        return hits if want_hits else rgb
 
     def render_frames(self, frames, image_width, image_height, row0=0, rows=None, out_rgb=None,
                       out_ppm=None, out_face=None, flags=RENDER_DEFAULT, timed=False, prepare_only=False,

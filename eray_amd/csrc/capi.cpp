@@ -20,6 +20,7 @@
 #include "../../include/eray_hip.h"
 #include "internal.hpp"
 #include "owners.hpp"
+#include "rays_args.hpp"
 
 using namespace eray::gpu;
 
@@ -1223,6 +1224,46 @@ int eray_render(eray_ctx* ctx, const eray_render_params* rp) {
         HIP_TRY(ctx, launch_frame(ctx, p));
         tag_frames(ctx, p.out_ppm, 0, 1, render_source(ctx, p, rp));
     }
+    return ERAY_OK;
+}
+
+// Ray queries (rays.hip): the batch's kernel on the context's stream, nothing else — no setup, no
+// copy back, so a call on an uploaded scene can be captured into a graph.
+int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* rp) {
+    if (int st = use_device(ctx)) return st;
+    const char* why = "";
+    if (int st = eray::check_rays_params(rp, ctx->objects.size(), &why)) return set_error(ctx, st, "eray_cast_rays: %s", why);
+    if (!rp->count) return ERAY_OK;
+    if (int st = sync_scene(ctx)) return st;
+    // bounces only matter when some material has a reflection output (engine.rs:181-182)
+    bool reflective = false;
+    for (auto& o : ctx->objects) {
+        const int32_t r = o.tout[4];
+        reflective |= r >= 0 ? !texel_is_color(o.tnodes[r].kind) : o.mat.reflection.data != nullptr;
+    }
+    RayBatch b;
+    std::memset(&b, 0, sizeof b);
+    FrameParams& p = b.f;
+    p.nframes = 1;
+    p.cx = ctx->camera.center[0];
+    p.cy = ctx->camera.center[1];
+    p.cz = ctx->camera.center[2];
+    p.tris = ctx->d_hot;
+    p.shade = ctx->d_shade;
+    p.objects = ctx->d_objs;
+    p.lights = ctx->d_lights;
+    p.nobj = (uint32_t)ctx->objects.size();
+    p.nlights = (uint32_t)ctx->lights.size();
+    p.total_tris = ctx->total_tris;
+    p.bounces = reflective ? rp->bounces : 0u;
+    b.rays = reinterpret_cast<const RayIn*>(rp->rays);
+    b.count = rp->count;
+    b.object = rp->object;
+    b.normalize = (rp->flags & ERAY_RAYS_NORMALIZE) ? 1u : 0u;
+    b.brute = (rp->flags & ERAY_RAYS_BRUTE_FORCE) ? 1u : 0u;
+    b.out_hit = reinterpret_cast<uint4*>(rp->out_hit);
+    b.out_rgb = rp->out_rgb;
+    HIP_TRY(ctx, launch_cast_rays(b, ctx->stream));
     return ERAY_OK;
 }
 

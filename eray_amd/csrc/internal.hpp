@@ -423,6 +423,25 @@ hipError_t launch_trace(const FrameParams& p, const LaunchCtx& lc, hipStream_t s
 hipError_t launch_write_ceiling(const FrameParams& p, uint32_t wgs_per_cu, const hipEvent_t (&t)[2], hipStream_t s);
 hipError_t launch_trace_cull(const FrameParams& p, hipStream_t s);
 
+// ------------------------------------------------------------- ray queries (rays.hip)
+// eray_cast_rays: a batch of caller-supplied rays against the scene.  `f` carries what cast_ray
+// reads of a frame (camera centre, triangle records, descriptors, lights, bounces), the rest zero.
+struct RayIn {  // eray_ray
+    float start[3], dir[3];
+};
+constexpr uint32_t kRayTile = 256;  // faces per LDS tile of the batch search (TriHot: 12 KB)
+struct RayBatch {
+    FrameParams f;
+    const RayIn* rays;
+    uint64_t count;
+    int32_t object;      // -1: every object, the closest by the camera's centre; k: object k alone
+    uint32_t normalize;  // dir goes through Ray::new
+    uint32_t brute;      // per-lane first_face, no tiles (ERAY_RAYS_BRUTE_FORCE)
+    uint4* out_hit;      // count x 3 words of 16 B (eray_ray_hit), or null
+    float* out_rgb;      // count x 3, or null
+};
+hipError_t launch_cast_rays(const RayBatch& b, hipStream_t s);
+
 // ------------------------------------------------------------- screen bins (bins.hip)
 // Device arrays of the binned objects' screen bins for one layout (camera size, row phase, the
 // binned objects), all preallocated: a camera's bins are rebuilt on the stream with no host

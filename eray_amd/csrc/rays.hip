@@ -1,0 +1,175 @@
+// rays.hip — ray queries on gfx950: Object<Built>::intersects (object.rs:58-81) and
+// Engine::cast_ray (engine.rs:112-216) for a batch of caller-supplied rays (eray_cast_rays).
+//
+// The frame kernel and the general tracer make their own rays from the camera; here the rays
+// come from the caller and go anywhere, so nothing camera-shaped (culling records, pixel
+// rectangles, screen bins) applies.  One lane is one ray; a 256-thread workgroup takes 256
+// consecutive rays at a time and strides over the batch.
+//
+// The search.  Per object (scene order): the bounding box (object.rs:59), then the first face by
+// index whose Triangle::intersects passes (object.rs:63-78).  The object's TriHot records stream
+// through an LDS tile of kRayTile faces, loaded by the whole workgroup with coalesced 16-B loads
+// and read back at a wave-uniform address (an LDS broadcast: three ds_read_b128 per face and
+// wave, no per-lane global loads).  A lane stops at its first passing face; a wave leaves the
+// tile once none of its lanes is still searching; the workgroup stops loading tiles once no wave
+// needs them — so an object whose box every ray of the workgroup fails (the loaded meshes'
+// (0,0,0) box for almost every ray) costs no face load at all.  With object == -1 the closest
+// object is the one whose hit point is strictly closer to the scene camera's centre than every
+// earlier object's (engine.rs:120-126: the camera's centre, not the ray's start).
+//
+// The winner's TriShade record and textures are read once per hit, after the object loop; a hit
+// record leaves as three 16-B stores.  out_rgb is cast_ray(ray, 0).sum() from that primary hit:
+// cast.hpp's fill_level and walk, whose shadow and reflected rays scan per lane as in trace.hip.
+//
+// ERAY_RAYS_BRUTE_FORCE is the plain form: every lane walks every face through its own loads
+// (cast.hpp first_face), no tiles, no workgroup-level skips — the same exact_test on the same
+// records, so the same u, v, t bit for bit (tests/test_gpu_rays.py compares the two).
+#include "cast.hpp"
+#include "device_math.hpp"
+#include "hit.hpp"
+#include "internal.hpp"
+
+namespace eray {
+namespace gpu {
+namespace {
+
+using namespace eray::dev;
+
+// An object's first passing face for the workgroup's 256 rays, through LDS tiles.  Every thread
+// of the workgroup must call (barriers); `inbox`: this lane's ray passed the object's box.
+// s_need[2][4]: each wave's "some lane still searches" flag, double-buffered by `phase` so that
+// a wave that has left a tile round cannot overwrite a flag another wave has yet to read.
+__device__ __forceinline__ int tile_first_face(const TriHot* tris, const ObjGeom& ob, bool inbox, f3 o, f3 d, float& u,
+                                               float& v, float& t, TriHot* s_tile, uint32_t (*s_need)[4],
+                                               uint32_t& phase) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float4* src = reinterpret_cast<const float4*>(tris + ob.tri_begin);
+    float4* dst = reinterpret_cast<float4*>(s_tile);
+    bool search = inbox;
+    int f = -1;
+    for (uint32_t t0 = 0; t0 < ob.tri_count; t0 += kRayTile) {  // (workgroup-uniform)
+        const bool wave_need = __any(search) != 0;
+        uint32_t* need = s_need[phase & 1u];
+        ++phase;
+        if (lane == 0) need[wave] = wave_need ? 1u : 0u;
+        __syncthreads();  // the flags are in; every wave has left the previous tile
+        if (!(need[0] | need[1] | need[2] | need[3])) break;  // (workgroup-uniform)
+        const uint32_t n = min(kRayTile, ob.tri_count - t0);
+        for (uint32_t q = threadIdx.x; q < 3 * n; q += 256) dst[q] = src[3 * (size_t)t0 + q];
+        __syncthreads();
+        if (!wave_need) continue;
+        for (uint32_t k = 0; k < n; ++k) {  // (wave-uniform: one LDS address per read)
+            const TriHot r = s_tile[k];
+            float uu, vv, tt;
+            if (search && exact_test(r, o, d, uu, vv, tt)) {
+                u = uu;
+                v = vv;
+                t = tt;
+                f = (int)(t0 + k);
+                search = false;
+            }
+            if (!__any(search)) break;
+        }
+    }
+    return f;
+}
+
+// Triangle::intersects' position and normal (primitives.rs:66-67) and RaycastHit's uv
+// (object.rs:70-72) of hit h, as the words of an eray_ray_hit; a miss: object -1, the rest 0.
+__device__ __forceinline__ void hit_record(const FrameParams& p, f3 o, f3 d, const Hit& h, uint4 (&q)[3]) {
+    q[0] = make_uint4(~0u, 0u, 0u, 0u);
+    q[1] = make_uint4(0u, 0u, 0u, 0u);
+    q[2] = make_uint4(0u, 0u, 0u, 0u);
+    if (h.f < 0) return;
+    const TriShade sh = p.shade[p.objects[h.o].g.tri_begin + (uint32_t)h.f];
+    const f3 P = add(o, mul(d, h.t));
+    const f3 na = mk3(sh.s0.x, sh.s0.y, sh.s0.z), nb = mk3(sh.s0.w, sh.s1.x, sh.s1.y);
+    const f3 nc = mk3(sh.s1.z, sh.s1.w, sh.s2.x);
+    const f3 N = normalize(add(add(mul(na, h.u), mul(nb, h.v)), mul(nc, h.t)));  // (t, not w: primitives.rs:67)
+    const float w = 1.0f - h.u - h.v;
+    const float uv0 = ((sh.s2.y * w) + (sh.s2.w * h.u)) + (sh.s3.y * h.v);
+    const float uv1 = ((sh.s2.z * w) + (sh.s3.x * h.u)) + (sh.s3.z * h.v);
+    q[0] = make_uint4(h.o, (uint32_t)h.f, __float_as_uint(P.x), __float_as_uint(P.y));
+    q[1] = make_uint4(__float_as_uint(P.z), __float_as_uint(N.x), __float_as_uint(N.y), __float_as_uint(N.z));
+    q[2] = make_uint4(__float_as_uint(uv0), __float_as_uint(uv1), __float_as_uint(h.u), __float_as_uint(h.v));
+}
+
+// kRgb: out_rgb is wanted (cast_ray's lights, shadows and, with kBounce, reflection levels).
+template <bool kRgb, bool kBounce>
+__global__ void __launch_bounds__(256) rays_kernel(RayBatch b) {
+    __shared__ TriHot s_tile[kRayTile];
+    __shared__ uint32_t s_need[2][4];
+    const FrameParams& p = b.f;
+    const f3 C = mk3(p.cx, p.cy, p.cz);
+    const uint32_t o0 = b.object >= 0 ? (uint32_t)b.object : 0u, o1 = b.object >= 0 ? o0 + 1u : p.nobj;
+    uint32_t phase = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < b.count; base += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = base + threadIdx.x;
+        const bool live = i < b.count;
+        f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, -1.0f);
+        if (live) {
+            const RayIn r = b.rays[i];
+            o = mk3(r.start[0], r.start[1], r.start[2]);
+            d = mk3(r.dir[0], r.dir[1], r.dir[2]);
+            if (b.normalize) d = normalize(d);  // Ray::new (raycasting.rs:16-21, vector.rs:150-158)
+        }
+        Hit h;
+        h.f = -1;
+        for (uint32_t oi = o0; oi < o1; ++oi) {  // scene order (engine.rs:116)
+            const ObjGeom ob = load_const(&p.objects[oi].g, 0);
+            float u, v, t;
+            int f = -1;
+            if (b.brute) {
+                if (live) f = first_face(p.tris, ob, o, d, u, v, t, nullptr);
+            } else {
+                f = tile_first_face(p.tris, ob, live && bbox_hit(ob, o, d), o, d, u, v, t, s_tile, s_need, phase);
+            }
+            closer(h, oi, f, u, v, t, o, d, C);
+        }
+        if (!live) continue;
+        if (b.out_hit) {
+            uint4 q[3];
+            hit_record(p, o, d, h, q);
+            uint4* dst = b.out_hit + 3 * i;
+            dst[0] = q[0];
+            dst[1] = q[1];
+            dst[2] = q[2];
+        }
+        if constexpr (kRgb) {
+            rgb c = miss_color();
+            if (h.f >= 0) {
+                Level L;
+                fill_level(p, o, d, h, L);
+                c = walk<kBounce>(p, L);
+            }
+            float* dst = b.out_rgb + 3 * i;
+            dst[0] = c.r;
+            dst[1] = c.g;
+            dst[2] = c.b;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_cast_rays(const RayBatch& b, hipStream_t s) {
+    if (!b.count) return hipSuccess;
+    if (!b.rays || (!b.out_hit && !b.out_rgb)) return hipErrorInvalidValue;
+    static const uint32_t cus = [] {
+        int dev = 0, n = 0;
+        return (hipGetDevice(&dev) == hipSuccess &&
+                hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+                   ? (uint32_t)n
+                   : 256u;
+    }();
+    // a workgroup per 256 rays, at most the 8 per CU the registers and the 12-KB tile allow at once
+    const uint64_t blocks = (b.count + 255u) / 256u, cap = 8ull * cus;
+    const dim3 grid((uint32_t)(blocks < cap ? blocks : cap));
+    if (!b.out_rgb) hipLaunchKernelGGL((rays_kernel<false, false>), grid, dim3(256), 0, s, b);
+    else if (b.f.bounces) hipLaunchKernelGGL((rays_kernel<true, true>), grid, dim3(256), 0, s, b);
+    else hipLaunchKernelGGL((rays_kernel<true, false>), grid, dim3(256), 0, s, b);
+    return hipGetLastError();
+}
+
+}  // namespace gpu
+}  // namespace eray

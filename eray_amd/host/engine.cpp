@@ -307,6 +307,49 @@ const Image<Color>& Engine::render() {  // engine.rs:46-81
     return image_;
 }
 
+Ray Ray::make(Vector3 start, Vector3 dir) {  // Ray::new (raycasting.rs:16-21): dir / |dir|, the fold from 0
+    float sq = 0.0f;
+    sq = sq + dir.x * dir.x;
+    sq = sq + dir.y * dir.y;
+    sq = sq + dir.z * dir.z;
+    const float len = std::sqrt(sq);
+    return Ray{start, Vector3(dir.x / len, dir.y / len, dir.z / len)};
+}
+
+std::vector<std::optional<RaycastHit>> Engine::cast_rays(const std::vector<Ray>& rays, int object) {
+    Device& d = Device::current();
+    if (scene_.dirty_) upload();
+    std::vector<std::optional<RaycastHit>> out(rays.size());
+    if (rays.empty()) return out;
+    std::vector<eray_ray> in(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i)
+        in[i] = eray_ray{{rays[i].start.x, rays[i].start.y, rays[i].start.z}, {rays[i].dir.x, rays[i].dir.y, rays[i].dir.z}};
+    DeviceBuffer d_in(in.size() * sizeof(eray_ray)), d_hit(in.size() * sizeof(eray_ray_hit));
+    d.check(eray_copy_to_device(d.ctx(), d_in.data(), in.data(), in.size() * sizeof(eray_ray)));
+    eray_rays_params p{};
+    p.rays = static_cast<const eray_ray*>(d_in.data());
+    p.count = in.size();
+    p.object = object;
+    p.out_hit = static_cast<eray_ray_hit*>(d_hit.data());
+    d.check(eray_cast_rays(d.ctx(), &p));
+    std::vector<eray_ray_hit> hits(in.size());
+    d.check(eray_copy_to_host(d.ctx(), hits.data(), d_hit.data(), hits.size() * sizeof(eray_ray_hit)));
+    for (size_t i = 0; i < hits.size(); ++i) {
+        const eray_ray_hit& h = hits[i];
+        if (h.object < 0) continue;
+        RaycastHit r;
+        r.object = (uint32_t)h.object;
+        r.face_index = (uint32_t)h.face;
+        r.position = Vector3(h.position[0], h.position[1], h.position[2]);
+        r.normal = Vector3(h.normal[0], h.normal[1], h.normal[2]);
+        r.uv = {h.uv[0], h.uv[1]};
+        r.u = h.u;
+        r.v = h.v;
+        out[i] = r;
+    }
+    return out;
+}
+
 const Image<Color>& Engine::render_to_path(const std::string& path) {  // engine.rs:86-98
     render();
     save_as_ppm(image_, path);

@@ -116,6 +116,23 @@ private:
     bool dirty_ = true;
 };
 
+// raycasting.rs:9-21: a start and a direction; Ray::make is Ray::new (the direction normalised,
+// vector.rs:150-158), an aggregate Ray{start, dir} keeps dir as given (a Ray's stored dir)
+struct Ray {
+    Vector3 start, dir;
+    static Ray make(Vector3 start, Vector3 dir);
+};
+
+// raycasting.rs:43-54 RaycastHit, with the hit's uv (object.rs:70-72) and barycentric u, v
+// (primitives.rs:60-61) in place of the material bundle Material::get derives from the uv
+struct RaycastHit {
+    uint32_t object = 0;      // index in Scene::objects()
+    uint32_t face_index = 0;  // relative to the object's first face
+    Vector3 position, normal;
+    std::array<float, 2> uv{};
+    float u = 0.0f, v = 0.0f;
+};
+
 // engine.rs:13-98
 class Engine {
 public:
@@ -126,6 +143,10 @@ public:
     const Image<Color>& render();
     // engine.rs:86-98: render + save_as_ppm (the PPM bytes come from the device, fused)
     const Image<Color>& render_to_path(const std::string& path);
+    // object.rs:58-81 Object::intersects for each ray, on the GPU (eray_cast_rays): object -1 the
+    // scene's closest object as cast_ray selects it (by the camera's centre, engine.rs:116-126),
+    // k >= 0 Object k alone; nullopt is a miss
+    std::vector<std::optional<RaycastHit>> cast_rays(const std::vector<Ray>& rays, int object = -1);
     // The anti-aliasing jitter stream's key (eray_render_params::aa_seed).  The reference draws
     // from the OS-seeded thread_rng; a new Engine picks a random seed likewise, and fixing it
     // makes anti-aliased renders reproducible.

@@ -28,6 +28,8 @@
  *                           Object::intersects object.rs:58-81, Triangle::intersects
  *                           primitives.rs:41-72, cast_ray shading engine.rs:112-216,
  *                           reaches_light engine.rs:218-228) fused with the PPM byte pack
+ *   eray_cast_rays          lib/object.rs:58-81 (Object::intersects -> RaycastHit) and
+ *                           lib/engine.rs:112-216 (Engine::cast_ray) for caller-supplied rays
  *   eray_pack_ppm           lib/image.rs:48-74 + lib/color.rs:31-37 (save_as_ppm body bytes)
  *   eray_gather_rows        lib/engine.rs:85-98 + lib/image.rs:48-74 across GPUs (row tiles, RCCL)
  *   eray_gather_frames      the same for a batch of frames (a frame ring), optionally sync-free
@@ -350,6 +352,71 @@ int eray_time_write_ceiling(eray_ctx* ctx, const eray_render_params* params, con
  * frames_per_launch frames per launch; others one (each camera rebuilds the screen bins). */
 int eray_render_camera_path_ring(eray_ctx* ctx, const eray_render_params* params, const eray_frame_ring* ring,
                                  const eray_camera* cameras, uint32_t n, float* mean_frame_ms);
+
+/* ------------------------------------------------------------------ ray queries -------- *
+ * Object<Built>::intersects(&Ray) -> Option<RaycastHit> (object.rs:58-81) and Engine::cast_ray
+ * (engine.rs:112-216) for rays the caller supplies: picking, G-buffer / visibility / collision
+ * queries, another camera model than pixel_to_ray, or a recorded jitter sequence.  Present since
+ * ABI version 6 builds that define ERAY_HAS_CAST_RAYS.                                          */
+#define ERAY_HAS_CAST_RAYS 1
+
+typedef struct eray_ray {           /* Ray (raycasting.rs:9-12)                        24 B */
+    float start[3];                 /* offset 0  */
+    float dir[3];                   /* offset 12 */
+} eray_ray;
+
+typedef struct eray_ray_hit {       /* RaycastHit (raycasting.rs:43-54)               48 B */
+    int32_t object;                 /* offset 0:  index from eray_scene_add_object, -1: no hit
+                                       (the rest of the record is then 0)                    */
+    int32_t face;                   /* offset 4:  RaycastHit::face_index, relative to the
+                                       object's first face (object.rs:63-78)                 */
+    float position[3];              /* offset 8:  start + dir * t (primitives.rs:66)         */
+    float normal[3];                /* offset 20: normalize(na*u + nb*v + nc*t)
+                                       (primitives.rs:67; t, not w)                          */
+    float uv[2];                    /* offset 32: a.uv*(1-u-v) + b.uv*u + c.uv*v
+                                       (object.rs:70-72, in that order)                      */
+    float u, v;                     /* offset 40, 44: Triangle::intersects' barycentric[0],
+                                       [1] (primitives.rs:60-61, 69)                             */
+} eray_ray_hit;
+
+typedef struct eray_rays_params {   /*                                                48 B */
+    const eray_ray* rays;           /* offset 0:  device, count rays                         */
+    uint64_t count;                 /* offset 8  */
+    int32_t object;                 /* offset 16: -1: the scene, as Engine::cast_ray selects
+                                       (below); k >= 0: Object k alone                       */
+    uint32_t bounces;               /* offset 20: Engine::bounces for out_rgb, <= 16         */
+    uint32_t flags;                 /* offset 24: ERAY_RAYS_*                                */
+    eray_ray_hit* out_hit;          /* offset 32: device (16-byte aligned) or NULL           */
+    float* out_rgb;                 /* offset 40: device or NULL: count x 3,
+                                       cast_ray(ray, 0).sum() (engine.rs:112-216,
+                                       color.rs:82-87)                                       */
+} eray_rays_params;
+
+#define ERAY_RAYS_NORMALIZE 1u      /* dir goes through Ray::new (raycasting.rs:16-21,
+                                       vector.rs:150-158); without it dir is used as given:
+                                       a Ray's stored dir                                    */
+#define ERAY_RAYS_BRUTE_FORCE 2u    /* every ray walks every face through its own loads: no LDS
+                                       tiles, no workgroup-level skips (A/B; same results)   */
+
+/* Per object: the bounding box first (object.rs:59, BoundingBox::intersects object.rs:327-379),
+ * then the first face BY INDEX whose Triangle::intersects passes (object.rs:63-78,
+ * primitives.rs:41-72).  object == -1: the objects in scene order, an object replacing the
+ * current one only when its hit point is strictly closer to the SCENE CAMERA's centre
+ * (engine.rs:120-126: the camera's centre, not the ray's start — so this mode reads the camera
+ * of eray_scene_set_camera, Camera::default() before the first call).  out_rgb is the left fold
+ * (color.rs:82-87) of cast_ray's list: per point light the shadow ray (engine.rs:130-141,
+ * reaches_light engine.rs:218-228), diffuse and specular terms (engine.rs:143-176) and the
+ * reflection bounce (engine.rs:181-191), then the ambient lights (engine.rs:197-208); the miss
+ * colour (0.1, 0.1, 0.2) for a ray that hits nothing (engine.rs:211-213).
+ * Errors: out_rgb together with object >= 0 (cast_ray has no single-object form), both outputs
+ * NULL, rays NULL with count > 0, an object index that is neither -1 nor an object of the scene,
+ * unknown flags, an out_hit that is not 16-byte aligned: ERAY_E_INVALID_ARGUMENT; bounces > 16:
+ * ERAY_E_UNSUPPORTED.  count == 0 returns ERAY_OK with nothing launched.  The call enqueues on
+ * the context's stream and makes no host round trip once the scene is on the device (the first
+ * call after a scene change uploads it), so it can be captured into a HIP graph.  A miss scans
+ * every face of every object whose box the ray passes: there is no acceleration structure for
+ * incoherent rays on large meshes (yet). */
+int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* params);
 
 /* ------------------------------------------------------------------ multi-GPU ----------- *
  * One process (one context) per GPU; a frame is split into row tiles and gathered on rank 0

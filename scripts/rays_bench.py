@@ -1,0 +1,141 @@
+"""Times eray_cast_rays against the brute-force render of the same rays (diagnostics, GPU only).
+
+    python scripts/rays_bench.py [--repeats 5] [--small-only] [--out FILE.json]
+
+Two cameras, main.rs's scene: C2 (1920x1080, cube.obj) and 3840x2160 over the 69,451-face
+stand-in mesh (bench.py's north-star scene).  The rays are the camera's own pixel-corner rays
+(camera.rs:57-76, restated here in np.float32 and checked against eray_render's faces), so
+eray_render with ERAY_RENDER_BRUTE_FORCE runs the same intersection tests plus shading — the code
+that existed before the ray queries — and is the yardstick of the hit-only query.
+
+Per camera and per form (hit records through the LDS tiles, hit records with
+ERAY_RAYS_BRUTE_FORCE, the brute-force render), `repeats` timings by device events around one
+call each, the forms alternating inside every repeat, after one untimed warm-up round; medians
+and the min..max spread.  One JSON line per camera.  No GPU: the context fails to open.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from eray_amd import capi, meshgen  # noqa: E402
+from eray_amd.frame import MainScene, fov_for  # noqa: E402
+from eray_amd.objfile import load_obj_file  # noqa: E402
+
+
+def camera_rays(center, fov, width: int, height: int, z_dist: float = 1.0) -> np.ndarray:
+    """Camera::pixel_to_ray(x / W, y / H) for every pixel (camera.rs:57-76; Ray::new normalises),
+    each operation in f32 in the reference's order: (H * W, 6) start | dir."""
+    f = np.float32
+    C = np.array(center, f)
+    vw = f(f(fov[0]) / f(fov[1])) * f(2.0)
+    horizontal, vertical = np.array([vw, 0, 0], f), np.array([0, 2, 0], f)
+    botleft = ((C - horizontal / f(2.0)) - vertical / f(2.0)) - np.array([0, 0, z_dist], f)
+    xf = (np.arange(width, dtype=f) / f(width))[None, :, None]
+    yf = (np.arange(height, dtype=f) / f(height))[:, None, None]
+    d = ((botleft + horizontal * xf) + vertical * yf) - C
+    sq = f(0.0) + d[..., 0] * d[..., 0]
+    sq = sq + d[..., 1] * d[..., 1]
+    sq = sq + d[..., 2] * d[..., 2]
+    d = d / np.sqrt(sq)[..., None]
+    rays = np.empty((height, width, 6), f)
+    rays[..., :3] = C
+    rays[..., 3:] = d
+    return rays.reshape(-1, 6)
+
+
+def summary(ms: list) -> dict:
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
+            "samples_ms": [round(v, 4) for v in ms]}
+
+
+def bench(name: str, mesh, width: int, height: int, repeats: int) -> dict:
+    stream = torch.cuda.Stream()
+    ctx = capi.Context(0)
+    ctx.set_stream(stream.cuda_stream)
+    fov = fov_for(width, height)
+    scene = MainScene(ctx, *mesh, width, height, texture=1024, fov=fov)
+    n = width * height
+    rays = ctx.to_device(camera_rays((0.0, 0.0, 5.0), fov, width, height))
+    hit = ctx.empty((n,), capi.HIT_DTYPE)
+    with torch.cuda.stream(stream):
+        rgb = torch.empty((height, width, 3), dtype=torch.float32, device="cuda")
+        face = torch.empty((height, width), dtype=torch.int32, device="cuda")
+    forms = {
+        "cast_rays_tiled": lambda: ctx.cast_rays_device(rays.ptr, n, out_hit=hit.ptr),
+        "cast_rays_brute": lambda: ctx.cast_rays_device(rays.ptr, n, out_hit=hit.ptr, flags=capi.RAYS_BRUTE_FORCE),
+        "render_brute": lambda: ctx.render(width, height, out_rgb=rgb.data_ptr(), out_face=face.data_ptr(),
+                                           flags=capi.RENDER_BRUTE_FORCE),
+    }
+    try:
+        # the same work: the query's faces are the render's
+        forms["render_brute"]()
+        forms["cast_rays_tiled"]()
+        ctx.synchronize()
+        h = hit.numpy()
+        got = np.where(h["object"] >= 0, h["face"], -1).reshape(height, width)
+        want = face.cpu().numpy()
+        if not np.array_equal(got, want):
+            raise AssertionError(f"{name}: cast_rays faces differ from eray_render's at {int((got != want).sum())} pixels")
+        forms["cast_rays_brute"]()
+        ctx.synchronize()
+        if hit.numpy().tobytes() != h.tobytes():
+            raise AssertionError(f"{name}: ERAY_RAYS_BRUTE_FORCE records differ from the tiled ones")
+        times = {k: [] for k in forms}
+        for rep in range(repeats + 1):  # round 0: warm-up
+            for k, fn in forms.items():
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record(stream)
+                fn()
+                t1.record(stream)
+                t1.synchronize()
+                if rep:
+                    times[k].append(t0.elapsed_time(t1))
+        out = {"camera": name, "width": width, "height": height, "faces": int(mesh[0].shape[0]), "rays": n,
+               "hit_rays": int((h["object"] >= 0).sum()), "repeats": repeats}
+        out.update({k: summary(v) for k, v in times.items()})
+        med = {k: out[k]["median_ms"] for k in forms}
+        out["tiled_over_render_brute"] = round(med["cast_rays_tiled"] / med["render_brute"], 4)
+        out["tiled_over_cast_rays_brute"] = round(med["cast_rays_tiled"] / med["cast_rays_brute"], 4)
+        return out
+    finally:
+        rays.free()
+        hit.free()
+        scene.close()
+        ctx.close()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--small-only", action="store_true", help="C2 only (skip the 69,451-face camera)")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    lines = [bench("C2 1920x1080 cube", load_obj_file(os.path.join(ROOT, "objects", "cube.obj")), 1920, 1080, a.repeats)]
+    print(json.dumps(lines[-1]), flush=True)
+    if not a.small_only:
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "standin_69451.obj")
+            meshgen.generate(path, 69451, 42)
+            mesh = load_obj_file(path)
+        lines.append(bench("3840x2160 69451 faces", mesh, 3840, 2160, a.repeats))
+        print(json.dumps(lines[-1]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()
