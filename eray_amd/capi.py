@@ -130,6 +130,11 @@ class RaysParams(C.Structure):  # eray_rays_params
                 ("flags", C.c_uint32), ("out_hit", C.c_void_p), ("out_rgb", C.c_void_p)]
 
 
+class RayAccelInfo(C.Structure):  # eray_ray_accel_info
+    _fields_ = [("objects", C.c_uint32), ("max_depth", C.c_uint32), ("nodes", C.c_uint64), ("faces", C.c_uint64),
+                ("unculled_faces", C.c_uint64), ("device_bytes", C.c_uint64), ("build_ms", C.c_float)]
+
+
 # eray_ray / eray_ray_hit as numpy records
 RAY_DTYPE = np.dtype([("start", np.float32, 3), ("dir", np.float32, 3)])
 HIT_DTYPE = np.dtype([("object", np.int32), ("face", np.int32), ("position", np.float32, 3),
@@ -192,6 +197,8 @@ SIGNATURES = {
     "eray_camera_size": (C.c_int, [C.POINTER(Camera), C.POINTER(_U), C.POINTER(_U)]),
     "eray_render": (C.c_int, [_P, C.POINTER(RenderParams)]),
     "eray_cast_rays": (C.c_int, [_P, C.POINTER(RaysParams)]),
+    "eray_scene_build_ray_accel": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
+    "eray_scene_drop_ray_accel": (C.c_int, [_P]),
     "eray_render_frames": (C.c_int, [_P, C.POINTER(RenderParams), _U, C.POINTER(C.c_float)]),
     "eray_render_prepare": (C.c_int, [_P, C.POINTER(RenderParams), _U]),
     "eray_render_camera_path": (C.c_int, [_P, C.POINTER(RenderParams), C.POINTER(Camera), _U,
@@ -582,6 +589,17 @@ class Context:
         f32 out): enqueued on the context's stream, nothing copied, nothing waited for."""
         p = RaysParams(rays_ptr or None, count, object, bounces, flags, out_hit or None, out_rgb or None)
         self._check(lib().eray_cast_rays(self._h, C.byref(p)))
+
+    def build_ray_accel(self, min_faces: int = 0) -> dict:
+        """eray_scene_build_ray_accel: a hierarchy for cast_rays over the objects of at least
+        min_faces faces (0: the library's default); synchronous.  Returns eray_ray_accel_info's
+        fields.  Any geometry change drops it; drop_ray_accel releases it."""
+        info = RayAccelInfo()
+        self._check(lib().eray_scene_build_ray_accel(self._h, min_faces, C.byref(info)))
+        return {name: getattr(info, name) for name, _ in RayAccelInfo._fields_}
+
+    def drop_ray_accel(self) -> None:
+        self._check(lib().eray_scene_drop_ray_accel(self._h))
 
     def cast_rays(self, rays, object=-1, bounces=0, normalize=False, brute_force=False, want_hits=True,
                   want_rgb=False):

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../include/eray_hip.h"
+#include "accel_build.hpp"
 #include "internal.hpp"
 #include "owners.hpp"
 #include "rays_args.hpp"
@@ -96,6 +98,7 @@ struct eray_ctx {
     DeviceBuf<float> d_raw;
     DeviceBuf<ObjectDesc> d_objs;
     DeviceBuf<LightDesc> d_lights;
+    RayAccel ray_accel;  // eray_scene_build_ray_accel's hierarchy; invalid after any geometry change
     // launch plans of eray_render_frames / eray_render_camera_path: HIP graphs of back-to-back
     // frames (chunks of up to kGraphFrames frames and remainders), each cached for the frame
     // parameters + stream + length + kind it was captured with; the least recently used is
@@ -929,6 +932,7 @@ int eray_scene_reset(eray_ctx* ctx) {
     ctx->lights.clear();
     ctx->camera = eray_camera{{0.0f, 0.0f, 0.0f}, {60.0f, 60.0f}, 1024u, 1.0f};
     ctx->geom_dirty = ctx->desc_dirty = true;
+    ctx->ray_accel.valid = false;
     return ERAY_OK;
 }
 
@@ -1036,6 +1040,7 @@ int eray_scene_add_object(eray_ctx* ctx, const eray_object* obj, uint32_t* index
     ctx->objects.push_back(std::move(h));
     if (index) *index = (uint32_t)(ctx->objects.size() - 1);
     ctx->geom_dirty = ctx->desc_dirty = true;
+    ctx->ray_accel.valid = false;
     return ERAY_OK;
 }
 
@@ -1263,7 +1268,82 @@ int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* rp) {
     b.brute = (rp->flags & ERAY_RAYS_BRUTE_FORCE) ? 1u : 0u;
     b.out_hit = reinterpret_cast<uint4*>(rp->out_hit);
     b.out_rgb = rp->out_rgb;
-    HIP_TRY(ctx, launch_cast_rays(b, ctx->stream));
+    RayAccelView av{nullptr, nullptr, nullptr, nullptr};
+    if (ctx->ray_accel.valid)  // (never a stale tree: every geometry change clears `valid`)
+        av = RayAccelView{ctx->ray_accel.objs, ctx->ray_accel.nodes,
+                          reinterpret_cast<const TriHot*>((const eray::accel::Hot*)ctx->ray_accel.hot), ctx->ray_accel.index};
+    HIP_TRY(ctx, launch_cast_rays(b, av, ctx->stream));
+    return ERAY_OK;
+}
+
+// The ray-query hierarchy (accel_build.hpp): built on the host from the device's own TriHot
+// records — the bits the kernels test — and uploaded; synchronous.
+int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
+    if (int st = use_device(ctx)) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int st = sync_scene(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
+    ctx->ray_accel.drop();
+    if (!min_faces) min_faces = 2 * kRayTile;
+    const uint32_t T = ctx->total_tris;
+    static_assert(sizeof(eray::accel::Hot) == sizeof(TriHot), "the builder reads the kernels' records");
+    std::vector<eray::accel::Hot> hot(T);
+    if (T) HIP_TRY(ctx, hipMemcpy(hot.data(), ctx->d_hot, sizeof(TriHot) * (size_t)T, hipMemcpyDeviceToHost));
+    std::vector<eray::accel::Object> objs(ctx->objects.size());
+    std::vector<eray::accel::Node> nodes;
+    std::vector<eray::accel::Hot> leaf;
+    std::vector<uint32_t> index;
+    eray_ray_accel_info out{};
+    uint32_t begin = 0;
+    for (size_t i = 0; i < ctx->objects.size(); ++i) {
+        const uint32_t n = ctx->objects[i].T;
+        std::memset(&objs[i], 0, sizeof objs[i]);
+        if (n >= min_faces) {
+            eray::accel::Built b;
+            const char* why = "";
+            if (nodes.size() + 2 * (size_t)n > 0x7fffffffu || leaf.size() + n > 0x7fffffffu ||
+                !eray::accel::build_object(hot.data() + begin, n, (uint32_t)nodes.size(), (uint32_t)leaf.size(),
+                                     eray::accel::kStackDepth, &b, &why))
+                return set_error(ctx, ERAY_E_UNSUPPORTED, "eray_scene_build_ray_accel: object %zu: %s", i,
+                                 *why ? why : "too many nodes");
+            objs[i] = b.obj;
+            nodes.insert(nodes.end(), b.nodes.begin(), b.nodes.end());
+            leaf.insert(leaf.end(), b.hot.begin(), b.hot.end());
+            index.insert(index.end(), b.index.begin(), b.index.end());
+            ++out.objects;
+            out.max_depth = std::max(out.max_depth, b.depth);
+            out.faces += n;
+            out.unculled_faces += b.unculled;
+        }
+        begin += n;
+    }
+    out.nodes = nodes.size();
+    if (out.objects) {
+        RayAccel& ra = ctx->ray_accel;
+        HIP_TRY(ctx, ra.objs.alloc(objs.size()));
+        HIP_TRY(ctx, ra.nodes.alloc(std::max<size_t>(nodes.size(), 1)));
+        HIP_TRY(ctx, ra.hot.alloc(std::max<size_t>(leaf.size(), 1)));
+        HIP_TRY(ctx, ra.index.alloc(std::max<size_t>(index.size(), 1)));
+        HIP_TRY(ctx, hipMemcpy(ra.objs, objs.data(), sizeof(eray::accel::Object) * objs.size(), hipMemcpyHostToDevice));
+        if (!nodes.empty())
+            HIP_TRY(ctx, hipMemcpy(ra.nodes, nodes.data(), sizeof(eray::accel::Node) * nodes.size(), hipMemcpyHostToDevice));
+        if (!leaf.empty()) {
+            HIP_TRY(ctx, hipMemcpy(ra.hot, leaf.data(), sizeof(eray::accel::Hot) * leaf.size(), hipMemcpyHostToDevice));
+            HIP_TRY(ctx, hipMemcpy(ra.index, index.data(), 4 * index.size(), hipMemcpyHostToDevice));
+        }
+        out.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
+                           sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
+        ra.valid = true;
+    }
+    out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = out;
+    return ERAY_OK;
+}
+
+int eray_scene_drop_ray_accel(eray_ctx* ctx) {
+    if (int st = use_device(ctx)) return st;
+    if (ctx->ray_accel.objs) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (queries in flight read it)
+    ctx->ray_accel.drop();
     return ERAY_OK;
 }
 

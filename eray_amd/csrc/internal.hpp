@@ -7,6 +7,8 @@
 #include <array>
 #include <vector>
 
+#include "accel_walk.hpp"
+
 namespace eray {
 namespace gpu {
 
@@ -440,7 +442,16 @@ struct RayBatch {
     uint4* out_hit;      // count x 3 words of 16 B (eray_ray_hit), or null
     float* out_rgb;      // count x 3, or null
 };
-hipError_t launch_cast_rays(const RayBatch& b, hipStream_t s);
+// The ray-query hierarchy of the scene (accel_walk.hpp; built by eray_scene_build_ray_accel): per
+// object a record (has == 0: the object keeps the LDS tiles), the nodes, and the leaf-ordered byte
+// copies of the face records with their original indices.  objs null: no hierarchy.
+struct RayAccelView {
+    const accel::Object* objs;
+    const accel::Node* nodes;
+    const TriHot* hot;
+    const uint32_t* index;
+};
+hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_t s);
 
 // ------------------------------------------------------------- screen bins (bins.hip)
 // Device arrays of the binned objects' screen bins for one layout (camera size, row phase, the

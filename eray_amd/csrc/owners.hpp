@@ -10,6 +10,8 @@
 #include <utility>
 #include <vector>
 
+#include "accel_walk.hpp"
+
 struct eray_ctx;
 
 namespace eray {
@@ -104,6 +106,25 @@ struct DeviceBuf : Buffer<T, hipFree> {
     // allocation freed and max(need, 1) elements allocated (contents are not kept).  An eray
     // status; defined in capi.cpp.
     int ensure(eray_ctx* ctx, size_t need);
+};
+
+// The scene's ray-query hierarchy on the device (accel_walk.hpp; capi.cpp
+// eray_scene_build_ray_accel): per object its record, the nodes, the leaf-ordered copies of the
+// face records (TriHot bytes) and their original indices.  `valid` falls with any geometry change
+// (a stale tree is never used); the memory is released by drop() or with the owner.
+struct RayAccel {
+    DeviceBuf<accel::Object> objs;
+    DeviceBuf<accel::Node> nodes;
+    DeviceBuf<accel::Hot> hot;
+    DeviceBuf<uint32_t> index;
+    bool valid = false;
+    void drop() {
+        valid = false;
+        (void)objs.release();
+        (void)nodes.release();
+        (void)hot.release();
+        (void)index.release();
+    }
 };
 
 // Pinned host memory; allocated with hipHostMallocMapped, `dev` is its device address.

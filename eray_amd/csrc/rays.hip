@@ -21,6 +21,18 @@
 // record leaves as three 16-B stores.  out_rgb is cast_ray(ray, 0).sum() from that primary hit:
 // cast.hpp's fill_level and walk, whose shadow and reflected rays scan per lane as in trace.hip.
 //
+// With a ray-query hierarchy (eray_scene_build_ray_accel; accel_walk.hpp, accel_build.hpp) the
+// objects that have one are searched by rays_accel_kernel instead: the box as before, then the
+// object's unculled faces in index order, then the tree, one lane one ray, with a per-lane stack of
+// kStackDepth node indices in LDS (laid out [level][thread]: a wave's lanes touch consecutive dwords, no bank conflict)
+// — no scratch, no spill.  A lane reads nodes and leaf faces through its own 16-B loads (three per
+// node, three per face): incoherent rays share nothing, and the nodes of a 70k-face mesh are well
+// under 1 MB, resident in L2.  The result is the smallest passing index with exact_test's u, v, t on
+// a byte copy of the same record, i.e. the scan's bits.  Rays the margin proof does not cover scan
+// per lane (first_face); objects without a hierarchy keep the tiles, and since the choice is per
+// object (wave- and workgroup-uniform) the tiles' barriers stay uniform.  out_rgb's shadow and
+// reflected rays keep cast.hpp's per-lane scan either way (cast.hpp is shared with trace.hip).
+//
 // ERAY_RAYS_BRUTE_FORCE is the plain form: every lane walks every face through its own loads
 // (cast.hpp first_face), no tiles, no workgroup-level skips — the same exact_test on the same
 // records, so the same u, v, t bit for bit (tests/test_gpu_rays.py compares the two).
@@ -94,6 +106,44 @@ __device__ __forceinline__ void hit_record(const FrameParams& p, f3 o, f3 d, con
     q[2] = make_uint4(__float_as_uint(uv0), __float_as_uint(uv1), __float_as_uint(h.u), __float_as_uint(h.v));
 }
 
+// A finished ray's outputs: its hit record and, with kRgb, cast_ray(ray, 0).sum() from that hit.
+template <bool kRgb, bool kBounce>
+__device__ __forceinline__ void store_ray(const RayBatch& b, uint64_t i, f3 o, f3 d, const Hit& h) {
+    const FrameParams& p = b.f;
+    if (b.out_hit) {
+        uint4 q[3];
+        hit_record(p, o, d, h, q);
+        uint4* dst = b.out_hit + 3 * i;
+        dst[0] = q[0];
+        dst[1] = q[1];
+        dst[2] = q[2];
+    }
+    if constexpr (kRgb) {
+        rgb c = miss_color();
+        if (h.f >= 0) {
+            Level L;
+            fill_level(p, o, d, h, L);
+            c = walk<kBounce>(p, L);
+        }
+        float* dst = b.out_rgb + 3 * i;
+        dst[0] = c.r;
+        dst[1] = c.g;
+        dst[2] = c.b;
+    }
+}
+
+// This lane's ray from the batch (dead lanes: a harmless ray), as rays_kernel loads its own.
+__device__ __forceinline__ void load_ray(const RayBatch& b, uint64_t i, bool live, f3& o, f3& d) {
+    o = mk3(0.0f, 0.0f, 0.0f);
+    d = mk3(0.0f, 0.0f, -1.0f);
+    if (live) {
+        const RayIn r = b.rays[i];
+        o = mk3(r.start[0], r.start[1], r.start[2]);
+        d = mk3(r.dir[0], r.dir[1], r.dir[2]);
+        if (b.normalize) d = normalize(d);  // Ray::new (raycasting.rs:16-21, vector.rs:150-158)
+    }
+}
+
 // kRgb: out_rgb is wanted (cast_ray's lights, shadows and, with kBounce, reflection levels).
 template <bool kRgb, bool kBounce>
 __global__ void __launch_bounds__(256) rays_kernel(RayBatch b) {
@@ -126,33 +176,76 @@ __global__ void __launch_bounds__(256) rays_kernel(RayBatch b) {
             }
             closer(h, oi, f, u, v, t, o, d, C);
         }
-        if (!live) continue;
-        if (b.out_hit) {
-            uint4 q[3];
-            hit_record(p, o, d, h, q);
-            uint4* dst = b.out_hit + 3 * i;
-            dst[0] = q[0];
-            dst[1] = q[1];
-            dst[2] = q[2];
-        }
-        if constexpr (kRgb) {
-            rgb c = miss_color();
-            if (h.f >= 0) {
-                Level L;
-                fill_level(p, o, d, h, L);
-                c = walk<kBounce>(p, L);
+        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h);
+    }
+}
+
+// The walk's stack of one lane: level k of thread t at s_stack[k][t].
+struct LaneStack {
+    uint32_t* base;
+    uint32_t n;
+    __device__ __forceinline__ void push(uint32_t x) { base[256u * n++] = x; }
+    __device__ __forceinline__ uint32_t pop() { return base[256u * --n]; }
+    __device__ __forceinline__ bool empty() const { return n == 0; }
+};
+
+// An object's first passing face through its hierarchy (accel_walk.hpp) for a ray that passed its
+// box; rays the margin proof does not cover scan per lane.
+__device__ __forceinline__ int accel_object_face(const RayBatch& b, const RayAccelView& a, const accel::Object& ao,
+                                                 const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t,
+                                                 uint32_t* stack) {
+    const float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z};
+    LaneStack st{stack, 0u};
+    const int f = accel::accel_first_face(ao, a.nodes, a.index, of, df, st, [&](uint32_t slot) {
+        const TriHot r = a.hot[slot];
+        float uu, vv, tt;
+        if (!exact_test(r, o, d, uu, vv, tt)) return false;
+        u = uu;
+        v = vv;
+        t = tt;
+        return true;
+    });
+    return f == accel::kAccelFallback ? first_face(b.f.tris, ob, o, d, u, v, t, nullptr) : f;
+}
+
+// rays_kernel's tiled form for a scene with a ray-query hierarchy: objects that have one go
+// through it, the others through the tiles (the choice is per object, so every barrier of
+// tile_first_face is reached by the whole workgroup).
+template <bool kRgb, bool kBounce>
+__global__ void __launch_bounds__(256) rays_accel_kernel(RayBatch b, RayAccelView a) {
+    __shared__ TriHot s_tile[kRayTile];
+    __shared__ uint32_t s_need[2][4];
+    __shared__ uint32_t s_stack[accel::kStackDepth][256];
+    const FrameParams& p = b.f;
+    const f3 C = mk3(p.cx, p.cy, p.cz);
+    const uint32_t o0 = b.object >= 0 ? (uint32_t)b.object : 0u, o1 = b.object >= 0 ? o0 + 1u : p.nobj;
+    uint32_t phase = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < b.count; base += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = base + threadIdx.x;
+        const bool live = i < b.count;
+        f3 o, d;
+        load_ray(b, i, live, o, d);
+        Hit h;
+        h.f = -1;
+        for (uint32_t oi = o0; oi < o1; ++oi) {  // scene order (engine.rs:116)
+            const ObjGeom ob = load_const(&p.objects[oi].g, 0);
+            const accel::Object ao = load_const(&a.objs[oi], 0);
+            float u, v, t;
+            int f = -1;
+            if (ao.has) {  // (workgroup-uniform)
+                if (live && bbox_hit(ob, o, d)) f = accel_object_face(b, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
+            } else {
+                f = tile_first_face(p.tris, ob, live && bbox_hit(ob, o, d), o, d, u, v, t, s_tile, s_need, phase);
             }
-            float* dst = b.out_rgb + 3 * i;
-            dst[0] = c.r;
-            dst[1] = c.g;
-            dst[2] = c.b;
+            closer(h, oi, f, u, v, t, o, d, C);
         }
+        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h);
     }
 }
 
 }  // namespace
 
-hipError_t launch_cast_rays(const RayBatch& b, hipStream_t s) {
+hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_t s) {
     if (!b.count) return hipSuccess;
     if (!b.rays || (!b.out_hit && !b.out_rgb)) return hipErrorInvalidValue;
     static const uint32_t cus = [] {
@@ -165,6 +258,12 @@ hipError_t launch_cast_rays(const RayBatch& b, hipStream_t s) {
     // a workgroup per 256 rays, at most the 8 per CU the registers and the 12-KB tile allow at once
     const uint64_t blocks = (b.count + 255u) / 256u, cap = 8ull * cus;
     const dim3 grid((uint32_t)(blocks < cap ? blocks : cap));
+    if (a.objs && !b.brute) {  // (the hierarchy's stack: 32 KB of LDS more, 3 workgroups per CU resident)
+        if (!b.out_rgb) hipLaunchKernelGGL((rays_accel_kernel<false, false>), grid, dim3(256), 0, s, b, a);
+        else if (b.f.bounces) hipLaunchKernelGGL((rays_accel_kernel<true, true>), grid, dim3(256), 0, s, b, a);
+        else hipLaunchKernelGGL((rays_accel_kernel<true, false>), grid, dim3(256), 0, s, b, a);
+        return hipGetLastError();
+    }
     if (!b.out_rgb) hipLaunchKernelGGL((rays_kernel<false, false>), grid, dim3(256), 0, s, b);
     else if (b.f.bounces) hipLaunchKernelGGL((rays_kernel<true, true>), grid, dim3(256), 0, s, b);
     else hipLaunchKernelGGL((rays_kernel<true, false>), grid, dim3(256), 0, s, b);

@@ -316,6 +316,19 @@ Ray Ray::make(Vector3 start, Vector3 dir) {  // Ray::new (raycasting.rs:16-21): 
     return Ray{start, Vector3(dir.x / len, dir.y / len, dir.z / len)};
 }
 
+Engine::RayAccelInfo Engine::build_ray_accel(uint32_t min_faces) {
+    Device& d = Device::current();
+    if (scene_.dirty_) upload();
+    eray_ray_accel_info i{};
+    d.check(eray_scene_build_ray_accel(d.ctx(), min_faces, &i));
+    return RayAccelInfo{i.objects, i.max_depth, i.nodes, i.faces, i.unculled_faces, i.device_bytes, i.build_ms};
+}
+
+void Engine::drop_ray_accel() {
+    Device& d = Device::current();
+    d.check(eray_scene_drop_ray_accel(d.ctx()));
+}
+
 std::vector<std::optional<RaycastHit>> Engine::cast_rays(const std::vector<Ray>& rays, int object) {
     Device& d = Device::current();
     if (scene_.dirty_) upload();

@@ -30,6 +30,8 @@
  *                           reaches_light engine.rs:218-228) fused with the PPM byte pack
  *   eray_cast_rays          lib/object.rs:58-81 (Object::intersects -> RaycastHit) and
  *                           lib/engine.rs:112-216 (Engine::cast_ray) for caller-supplied rays
+ *   eray_scene_build_ray_accel  a hierarchy for eray_cast_rays that keeps object.rs:63-78's choice
+ *                           (the first passing face by index) and its bits
  *   eray_pack_ppm           lib/image.rs:48-74 + lib/color.rs:31-37 (save_as_ppm body bytes)
  *   eray_gather_rows        lib/engine.rs:85-98 + lib/image.rs:48-74 across GPUs (row tiles, RCCL)
  *   eray_gather_frames      the same for a batch of frames (a frame ring), optionally sync-free
@@ -414,9 +416,36 @@ typedef struct eray_rays_params {   /*                                          
  * ERAY_E_UNSUPPORTED.  count == 0 returns ERAY_OK with nothing launched.  The call enqueues on
  * the context's stream and makes no host round trip once the scene is on the device (the first
  * call after a scene change uploads it), so it can be captured into a HIP graph.  A miss scans
- * every face of every object whose box the ray passes: there is no acceleration structure for
- * incoherent rays on large meshes (yet). */
+ * every face of every object whose box the ray passes, unless the scene has a ray-query hierarchy
+ * (eray_scene_build_ray_accel below): objects that have one are then searched through it, with
+ * the same records as results, bit for bit.  ERAY_RAYS_BRUTE_FORCE stays the per-ray scan.  The
+ * shadow and reflected rays of out_rgb scan per ray either way. */
 int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* params);
+
+/* A hierarchy for eray_cast_rays over the objects of at least min_faces faces (0: 512, two of the
+ * scan's 256-face tiles; smaller objects gain nothing over the tiles).  It returns the reference's
+ * face — the first by index that passes Triangle::intersects in f32, not the nearest — for every
+ * ray: a subtree is skipped only where no face of it can pass (the proof is in
+ * eray_amd/csrc/accel_build.hpp); faces it cannot prove a margin for (unculled_faces: the cube's,
+ * with |n| = 4) are tested by every ray, and rays it does not cover (a non-finite component, a
+ * direction or start beyond 2^40) scan the object's faces as before.  The build is explicit and
+ * synchronous: it uploads the scene, waits for the stream, reads the device's face records back
+ * and builds on the host.  Any geometry change (eray_scene_add_object, eray_scene_reset) drops
+ * the hierarchy silently — queries then run as without one — and so does
+ * eray_scene_drop_ray_accel; material, light and camera changes keep it.  A second build replaces
+ * the first.  Errors: ERAY_E_UNSUPPORTED for a tree deeper than the traversal stack (32 levels: not
+ * reachable below the scene's face limit).  Present in builds that define ERAY_HAS_RAY_ACCEL. */
+#define ERAY_HAS_RAY_ACCEL 1
+typedef struct eray_ray_accel_info {   /*                                                48 B */
+    uint32_t objects;               /* offset 0:  objects that got a hierarchy               */
+    uint32_t max_depth;             /* offset 4:  levels of the deepest tree                 */
+    uint64_t nodes, faces;          /* offset 8, 16: nodes; faces under hierarchies          */
+    uint64_t unculled_faces;        /* offset 24: faces every ray tests (no provable margin) */
+    uint64_t device_bytes;          /* offset 32 */
+    float build_ms;                 /* offset 40: host wall time of the build                */
+} eray_ray_accel_info;
+int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info /* may be NULL */);
+int eray_scene_drop_ray_accel(eray_ctx* ctx);
 
 /* ------------------------------------------------------------------ multi-GPU ----------- *
  * One process (one context) per GPU; a frame is split into row tiles and gathered on rank 0

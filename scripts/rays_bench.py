@@ -1,6 +1,6 @@
 """Times eray_cast_rays against the brute-force render of the same rays (diagnostics, GPU only).
 
-    python scripts/rays_bench.py [--repeats 5] [--small-only] [--out FILE.json]
+    python scripts/rays_bench.py [--repeats 5] [--small-only] [--no-1m] [--out FILE.json]
 
 Two cameras, main.rs's scene: C2 (1920x1080, cube.obj) and 3840x2160 over the 69,451-face
 stand-in mesh (bench.py's north-star scene).  The rays are the camera's own pixel-corner rays
@@ -9,9 +9,17 @@ eray_render with ERAY_RENDER_BRUTE_FORCE runs the same intersection tests plus s
 that existed before the ray queries — and is the yardstick of the hit-only query.
 
 Per camera and per form (hit records through the LDS tiles, hit records with
-ERAY_RAYS_BRUTE_FORCE, the brute-force render), `repeats` timings by device events around one
-call each, the forms alternating inside every repeat, after one untimed warm-up round; medians
-and the min..max spread.  One JSON line per camera.  No GPU: the context fails to open.
+ERAY_RAYS_BRUTE_FORCE, the brute-force render, hit records through the ray-query hierarchy),
+`repeats` timings by device events around one call each, the forms alternating inside every
+repeat, after one untimed warm-up round; medians and the min..max spread.  The hierarchy form
+runs in a second context holding the same scene plus eray_scene_build_ray_accel's hierarchy (no
+flag selects the tiles once a hierarchy exists), on the same stream; its records are checked
+byte for byte against the tiled ones.
+
+Then the incoherent workload the hierarchy is for: 2^22 rays from the radius-3 sphere toward
+targets uniform in [-1, 1]^3 against the 69,451-face mesh with its true box (tiles against
+hierarchy), and 2^20 such rays against the 1M-face mesh (--no-1m skips it), with each mesh's build
+time and device bytes.  One JSON line per workload.  No GPU: the context fails to open.
 """
 from __future__ import annotations
 
@@ -66,6 +74,10 @@ def bench(name: str, mesh, width: int, height: int, repeats: int) -> dict:
     ctx.set_stream(stream.cuda_stream)
     fov = fov_for(width, height)
     scene = MainScene(ctx, *mesh, width, height, texture=1024, fov=fov)
+    actx = capi.Context(0)  # the same scene with a hierarchy
+    actx.set_stream(stream.cuda_stream)
+    ascene = MainScene(actx, *mesh, width, height, texture=1024, fov=fov)
+    info = actx.build_ray_accel()
     n = width * height
     rays = ctx.to_device(camera_rays((0.0, 0.0, 5.0), fov, width, height))
     hit = ctx.empty((n,), capi.HIT_DTYPE)
@@ -77,6 +89,7 @@ def bench(name: str, mesh, width: int, height: int, repeats: int) -> dict:
         "cast_rays_brute": lambda: ctx.cast_rays_device(rays.ptr, n, out_hit=hit.ptr, flags=capi.RAYS_BRUTE_FORCE),
         "render_brute": lambda: ctx.render(width, height, out_rgb=rgb.data_ptr(), out_face=face.data_ptr(),
                                            flags=capi.RENDER_BRUTE_FORCE),
+        "cast_rays_accel": lambda: actx.cast_rays_device(rays.ptr, n, out_hit=hit.ptr),
     }
     try:
         # the same work: the query's faces are the render's
@@ -92,6 +105,10 @@ def bench(name: str, mesh, width: int, height: int, repeats: int) -> dict:
         ctx.synchronize()
         if hit.numpy().tobytes() != h.tobytes():
             raise AssertionError(f"{name}: ERAY_RAYS_BRUTE_FORCE records differ from the tiled ones")
+        forms["cast_rays_accel"]()
+        ctx.synchronize()
+        if hit.numpy().tobytes() != h.tobytes():
+            raise AssertionError(f"{name}: the hierarchy's records differ from the tiled ones")
         times = {k: [] for k in forms}
         for rep in range(repeats + 1):  # round 0: warm-up
             for k, fn in forms.items():
@@ -108,18 +125,88 @@ def bench(name: str, mesh, width: int, height: int, repeats: int) -> dict:
         med = {k: out[k]["median_ms"] for k in forms}
         out["tiled_over_render_brute"] = round(med["cast_rays_tiled"] / med["render_brute"], 4)
         out["tiled_over_cast_rays_brute"] = round(med["cast_rays_tiled"] / med["cast_rays_brute"], 4)
+        out["accel_over_tiled"] = round(med["cast_rays_accel"] / med["cast_rays_tiled"], 4)
+        out["accel_info"] = info
         return out
     finally:
         rays.free()
         hit.free()
+        ascene.close()
+        actx.close()
         scene.close()
         ctx.close()
+
+
+def sphere_rays(n: int, seed: int = 7) -> np.ndarray:
+    """n rays from the radius-3 sphere toward targets uniform in [-1, 1]^3 (dir not normalised)."""
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=(n, 3))
+    start = 3.0 * v / np.linalg.norm(v, axis=1, keepdims=True)
+    target = rng.uniform(-1, 1, (n, 3))
+    return np.ascontiguousarray(np.concatenate([start, target - start], axis=1), np.float32)
+
+
+def bench_incoherent(name: str, mesh, nrays: int, repeats: int) -> dict:
+    """Incoherent rays against one mesh with its true box: the tiles (context without a hierarchy)
+    against the hierarchy (a second context), alternating; records compared byte for byte."""
+    stream = torch.cuda.Stream()
+    lo, hi = mesh[0].reshape(-1, 3).min(0), mesh[0].reshape(-1, 3).max(0)
+    ctxs = []
+    for _ in range(2):
+        c = capi.Context(0)
+        c.set_stream(stream.cuda_stream)
+        c.set_camera(capi.make_camera((0.0, 0.0, 5.0), (60.0, 60.0), 64, 1.0))
+        c.add_object(*mesh, tuple(lo), tuple(hi))
+        ctxs.append(c)
+    ctx, actx = ctxs
+    info = actx.build_ray_accel()
+    rays = ctx.to_device(sphere_rays(nrays))
+    hit = ctx.empty((nrays,), capi.HIT_DTYPE)
+    forms = {
+        "cast_rays_tiled": lambda: ctx.cast_rays_device(rays.ptr, nrays, out_hit=hit.ptr, flags=capi.RAYS_NORMALIZE),
+        "cast_rays_accel": lambda: actx.cast_rays_device(rays.ptr, nrays, out_hit=hit.ptr, flags=capi.RAYS_NORMALIZE),
+    }
+    try:
+        forms["cast_rays_tiled"]()
+        ctx.synchronize()
+        h = hit.numpy()
+        forms["cast_rays_accel"]()
+        ctx.synchronize()
+        if hit.numpy().tobytes() != h.tobytes():
+            raise AssertionError(f"{name}: the hierarchy's records differ from the tiled ones")
+        times = {k: [] for k in forms}
+        for rep in range(repeats + 1):  # round 0: warm-up
+            for k, fn in forms.items():
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record(stream)
+                fn()
+                t1.record(stream)
+                t1.synchronize()
+                if rep:
+                    times[k].append(t0.elapsed_time(t1))
+        out = {"workload": name, "faces": int(mesh[0].shape[0]), "rays": nrays, "hit_rays": int((h["object"] >= 0).sum()),
+               "repeats": repeats, "accel_info": info}
+        out.update({k: summary(v) for k, v in times.items()})
+        out["tiled_over_accel"] = round(out["cast_rays_tiled"]["median_ms"] / out["cast_rays_accel"]["median_ms"], 2)
+        return out
+    finally:
+        rays.free()
+        hit.free()
+        for c in ctxs:
+            c.close()
+
+
+def generated_mesh(triangles: int, seed: int):
+    v, n, t, F, _, _ = meshgen.displaced_sphere(triangles, seed)
+    return (v[F].reshape(triangles, 9).astype(np.float32), n[F].reshape(triangles, 9).astype(np.float32),
+            t[F].reshape(triangles, 6).astype(np.float32))
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--small-only", action="store_true", help="C2 only (skip the 69,451-face camera)")
+    ap.add_argument("--no-1m", action="store_true", help="skip the 1M-face incoherent workload")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     lines = [bench("C2 1920x1080 cube", load_obj_file(os.path.join(ROOT, "objects", "cube.obj")), 1920, 1080, a.repeats)]
@@ -131,6 +218,13 @@ def main() -> None:
             mesh = load_obj_file(path)
         lines.append(bench("3840x2160 69451 faces", mesh, 3840, 2160, a.repeats))
         print(json.dumps(lines[-1]), flush=True)
+        lines.append(bench_incoherent("2^22 sphere rays, 69451 faces, true box", generated_mesh(**meshgen.STANDIN_70K), 1 << 22,
+                                      a.repeats))
+        print(json.dumps(lines[-1]), flush=True)
+        if not a.no_1m:
+            lines.append(bench_incoherent("2^20 sphere rays, 1M faces, true box", generated_mesh(**meshgen.SYNTH_1M), 1 << 20,
+                                          a.repeats))
+            print(json.dumps(lines[-1]), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             for ln in lines:
