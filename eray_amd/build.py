@@ -25,7 +25,7 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "liberay_hip.so")
 
 SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "comm.cpp",
-           "objload.cpp", "accel_build.cpp"]
+           "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
             f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),
@@ -101,9 +101,15 @@ ROCM_LIB = "/opt/rocm/lib"
 ACCEL_WALK_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-pthread"]
 
 
+# tests/cpp/accel_dev_main.cpp: the same flags; what it compiles with and depends on
+ACCEL_DEV_SOURCES = [os.path.join(CSRC, "accel_build.cpp"), os.path.join(CSRC, "accel_check.cpp")]
+ACCEL_DEV_HEADERS = ["accel_build.hpp", "accel_walk.hpp", "accel_margin.hpp", "accel_layout.hpp", "accel_check.hpp"]
+
+
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
-    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, accel_walk_main).  Plain g++: the
+    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, accel_walk_main,
+    accel_dev_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -138,7 +144,8 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     for name, src in (("eray_main", os.path.join(host, "main.cpp")),
                       ("test_host", os.path.join(ROOT, "tests", "cpp", "test_host.cpp")),
                       ("test_rays", os.path.join(ROOT, "tests", "cpp", "test_rays.cpp")),
-                      ("test_accel", os.path.join(ROOT, "tests", "cpp", "test_accel.cpp"))):
+                      ("test_accel", os.path.join(ROOT, "tests", "cpp", "test_accel.cpp")),
+                      ("test_accel_dev", os.path.join(ROOT, "tests", "cpp", "test_accel_dev.cpp"))):
         exe = os.path.join(BIN_DIR, name)
         if force or not _newer(exe, [src, HOST_LIB] + headers):
             run([cxx, *flags, src, "-o", exe, "-L" + LIB_DIR, "-leray_host", *link])
@@ -146,8 +153,15 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     # the ray-query hierarchy on the CPU: the builder and the shared walk, no GPU library
     walk_src = [os.path.join(ROOT, "tests", "cpp", "accel_walk_main.cpp"), os.path.join(CSRC, "accel_build.cpp")]
     exe = os.path.join(BIN_DIR, "accel_walk_main")
-    if force or not _newer(exe, walk_src + [os.path.join(CSRC, "accel_build.hpp"), os.path.join(CSRC, "accel_walk.hpp")]):
+    if force or not _newer(exe, walk_src + [os.path.join(CSRC, h) for h in ("accel_build.hpp", "accel_walk.hpp",
+                                                                            "accel_margin.hpp")]):
         run([cxx, *ACCEL_WALK_FLAGS, *walk_src, "-o", exe])
+    outs.append(exe)
+    # the device-side builder emulated on the CPU with the headers its kernels share, and the checker
+    dev_src = [os.path.join(ROOT, "tests", "cpp", "accel_dev_main.cpp"), *ACCEL_DEV_SOURCES]
+    exe = os.path.join(BIN_DIR, "accel_dev_main")
+    if force or not _newer(exe, dev_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
+        run([cxx, *ACCEL_WALK_FLAGS, *dev_src, "-o", exe])
     outs.append(exe)
     return outs
 

@@ -198,6 +198,7 @@ SIGNATURES = {
     "eray_render": (C.c_int, [_P, C.POINTER(RenderParams)]),
     "eray_cast_rays": (C.c_int, [_P, C.POINTER(RaysParams)]),
     "eray_scene_build_ray_accel": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
+    "eray_scene_build_ray_accel_device": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
     "eray_scene_drop_ray_accel": (C.c_int, [_P]),
     "eray_render_frames": (C.c_int, [_P, C.POINTER(RenderParams), _U, C.POINTER(C.c_float)]),
     "eray_render_prepare": (C.c_int, [_P, C.POINTER(RenderParams), _U]),
@@ -246,6 +247,7 @@ DEBUG_SIGNATURES = {
     "eray_debug_gather_check": (C.c_int, [C.POINTER(C.c_uint32), _U, _U, _U, _U, _U, C.c_uint64, _P]),
     "eray_debug_plan_verdict": (C.c_int, [C.POINTER(C.c_int32), _U, _U]),
     "eray_debug_gather_replan": (C.c_int, [_U, _U, C.c_uint64, _U, C.c_uint64]),
+    "eray_debug_ray_accel_check": (C.c_int, [_P, C.c_char_p, _U]),
 }
 
 _lib = None
@@ -590,13 +592,25 @@ class Context:
         p = RaysParams(rays_ptr or None, count, object, bounces, flags, out_hit or None, out_rgb or None)
         self._check(lib().eray_cast_rays(self._h, C.byref(p)))
 
-    def build_ray_accel(self, min_faces: int = 0) -> dict:
+    def build_ray_accel(self, min_faces: int = 0, device: bool = False) -> dict:
         """eray_scene_build_ray_accel: a hierarchy for cast_rays over the objects of at least
-        min_faces faces (0: the library's default); synchronous.  Returns eray_ray_accel_info's
-        fields.  Any geometry change drops it; drop_ray_accel releases it."""
+        min_faces faces (0: the library's default); synchronous.  device=True builds it on the GPU
+        from the resident records (eray_scene_build_ray_accel_device) instead of on the host.
+        Returns eray_ray_accel_info's fields.  Any geometry change drops it; drop_ray_accel
+        releases it."""
         info = RayAccelInfo()
-        self._check(lib().eray_scene_build_ray_accel(self._h, min_faces, C.byref(info)))
+        fn = lib().eray_scene_build_ray_accel_device if device else lib().eray_scene_build_ray_accel
+        self._check(fn(self._h, min_faces, C.byref(info)))
         return {name: getattr(info, name) for name, _ in RayAccelInfo._fields_}
+
+    def check_ray_accel(self) -> str:
+        """eray_debug_ray_accel_check (diagnostics): '' when the current hierarchy holds every
+        invariant of accel_check.hpp, else the first violated one."""
+        msg = C.create_string_buffer(512)
+        st = lib().eray_debug_ray_accel_check(self._h, msg, len(msg))
+        if st != OK and not msg.value:
+            self._check(st)
+        return msg.value.decode()
 
     def drop_ray_accel(self) -> None:
         self._check(lib().eray_scene_drop_ray_accel(self._h))

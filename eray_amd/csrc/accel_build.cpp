@@ -9,27 +9,12 @@ namespace eray {
 namespace accel {
 namespace {
 
-constexpr double kU = 0x1p-24;
-constexpr double kDetShare = 0.2e-6;  // kappa |d|inf may reach this much of the 1e-6 threshold
-constexpr double kDetFloor = 0.75e-6;
-constexpr double kMarginMax = 1e30;
-
 struct V3 {
     double x, y, z;
 };
 V3 e1_of(const Hot& r) { return {r.q[0], r.q[1], r.q[2]}; }
 V3 e2_of(const Hot& r) { return {r.q[3], r.q[4], r.q[5]}; }
-V3 n_of(const Hot& r) { return {r.q[6], r.q[7], r.q[8]}; }
 V3 a_of(const Hot& r) { return {r.q[9], r.q[10], r.q[11]}; }
-double n1(V3 v) { return std::fabs(v.x) + std::fabs(v.y) + std::fabs(v.z); }
-double n2(V3 v) { return std::sqrt(v.x * v.x + v.y * v.y + v.z * v.z); }
-
-// the smallest float >= x (x finite, >= 0), one step further for the double arithmetic before it
-float up(double x) {
-    float f = (float)x;
-    if ((double)f < x) f = std::nextafterf(f, INFINITY);
-    return std::nextafterf(f, INFINITY);
-}
 
 struct Ctx {
     const Hot* faces;
@@ -123,22 +108,7 @@ uint32_t build_node(Ctx& c, uint32_t lo, uint32_t hi, uint32_t level) {
 
 }  // namespace
 
-FaceMargin face_margin(const Hot& r) {
-    FaceMargin m{0.0, 0.0, 0.0, 0.0, false};
-    for (float x : r.q)
-        if (!std::isfinite(x)) return m;
-    const V3 e1 = e1_of(r), e2 = e2_of(r), n = n_of(r), a = a_of(r);
-    const V3 N = {e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x};
-    const double dn = n1({n.x - N.x, n.y - N.y, n.z - N.z});
-    const double E1 = n2(e1), E2 = n2(e2);
-    m.kappa = 2.01 * kU * n1(n) + 1.001 * dn + 1e-30;
-    m.alpha = 8.0 * kU * (n1(e2) * E1 + n1(e1) * E2) / kDetFloor;
-    m.beta = 1.001 * m.kappa * (E1 + E2) / kDetFloor + m.alpha * n1(a);
-    m.gamma = 5.2 * kU * (E1 + E2) + 1e-30;
-    m.culled = m.kappa <= 1.9 * m.alpha * kDetShare && m.alpha <= kAlphaMax && std::isfinite(m.alpha) && std::isfinite(m.beta) &&
-               std::isfinite(m.gamma) && m.alpha <= kMarginMax && m.beta <= kMarginMax && m.gamma <= kMarginMax;
-    return m;
-}
+FaceMargin face_margin(const Hot& r) { return face_margin_of(r); }
 
 bool build_object(const Hot* faces, uint32_t T, uint32_t node_base, uint32_t slot_base, uint32_t max_depth, Built* out,
                   const char** why) {

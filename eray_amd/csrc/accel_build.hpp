@@ -63,17 +63,13 @@
 #include <cstdint>
 #include <vector>
 
+#include "accel_margin.hpp"
 #include "accel_walk.hpp"
 
 namespace eray {
 namespace accel {
 
-constexpr double kAlphaMax = 0.25;
-
-struct FaceMargin {
-    double alpha, beta, gamma, kappa;
-    bool culled;  // false: the face belongs to the unculled list
-};
+// (kAlphaMax, FaceMargin and the margin's arithmetic: accel_margin.hpp, shared with the device build)
 FaceMargin face_margin(const Hot& r);
 
 struct Built {

@@ -1,0 +1,38 @@
+// accel_dev.hpp — the device-side builder of the ray-query hierarchy (accel_dev.hip): the same
+// records as accel_build.hpp's host builder (accel_walk.hpp Object / Node, leaf-ordered TriHot
+// copies, the index array), built on a stream from the resident face records.  Host interface
+// only; capi.cpp's eray_scene_build_ray_accel_device owns the context side.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "internal.hpp"
+#include "owners.hpp"
+
+namespace eray {
+namespace gpu {
+
+struct AccelDevObject {  // an object that gets a hierarchy
+    uint32_t index;      // in the scene
+    uint32_t hot_begin;  // its first record in the scene's TriHot array
+    uint32_t faces;
+};
+
+struct AccelDevInfo {
+    uint32_t max_depth = 0;
+    uint64_t nodes = 0, unculled = 0;
+};
+
+// Builds the hierarchy of `covered` (scene order) into ra (objs: nobj records, zero for the other
+// objects) on stream s and waits for it.  One device-to-host copy: 16 B of counters per covered
+// object (culled, unculled, status); no face record leaves the device.  Temporaries are released
+// before it returns.  *refuse (when set on return, with hipSuccess) names why the scene is not
+// supported; ra is then left dropped.
+hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObject>& covered, size_t nobj, RayAccel& ra,
+                              hipStream_t s, AccelDevInfo* info, const char** refuse);
+
+}  // namespace gpu
+}  // namespace eray

@@ -1,0 +1,222 @@
+// accel_layout.hpp — the device-side builder's arithmetic (accel_dev.hip), host/device-neutral so
+// that tests/cpp/accel_dev_main.cpp runs the same code on the CPU: the Morton key of a centroid,
+// the tree's layout from the number of culled faces alone, and the leaf / inner-node functions.
+//
+// ORDER.  The culled faces of an object are sorted by (key, index): key = 63 bits, 21 per axis of
+// the centroid a + (e1 + e2) / 3 quantised in double within the object's centroid bounds (a
+// zero-extent axis: code 0).
+//
+// TOPOLOGY.  The balanced split of that order with the host builder's arithmetic: a range of
+// count <= kLeafFaces is a leaf, otherwise mid = lo + count / 2.  The counts of one level differ by
+// at most one (count of node j of level L = floor((C + rev_L(j)) / 2^L)), so with
+//     F = the first level whose smallest count floor(C / 2^F) is <= kLeafFaces
+// levels 0 .. F are complete (2^L nodes, heap numbering 2^L - 1 + j) and at most one more level
+// exists: the two leaves under every node of level F that still holds kLeafFaces + 1 faces.  There
+// are `extra` = C - kLeafFaces * 2^F such nodes when floor(C / 2^F) == kLeafFaces; the one at
+// position j starts at lo = kLeafFaces * j + (how many of them precede it), so its children are
+// numbered 2^(F+1) - 1 + 2 (lo - kLeafFaces j) and the next.  Node count and depth are the host
+// build's for the same C.
+#pragma once
+
+#include "accel_margin.hpp"
+#include "accel_walk.hpp"
+
+namespace eray {
+namespace accel {
+
+// 21 bits of v spread to every third bit
+ERAY_HD uint64_t spread3(uint64_t v) {
+    v &= 0x1fffffull;
+    v = (v | v << 32) & 0x1f00000000ffffull;
+    v = (v | v << 16) & 0x1f0000ff0000ffull;
+    v = (v | v << 8) & 0x100f00f00f00f00full;
+    v = (v | v << 4) & 0x10c30c30c30c30c3ull;
+    v = (v | v << 2) & 0x1249249249249249ull;
+    return v;
+}
+
+// c in [lo, hi] to 0 .. 2^21 - 1
+ERAY_HD uint32_t morton_code(double c, double lo, double hi) {
+    const double ext = hi - lo;
+    if (!(ext > 0.0)) return 0u;
+    const double q = (c - lo) / ext * 2097152.0;
+    if (!(q > 0.0)) return 0u;
+    return q >= 2097151.0 ? 2097151u : (uint32_t)q;
+}
+
+ERAY_HD void centroid_of(const Hot& r, double* c) {
+    c[0] = (double)r.q[9] + ((double)r.q[0] + (double)r.q[3]) / 3.0;
+    c[1] = (double)r.q[10] + ((double)r.q[1] + (double)r.q[4]) / 3.0;
+    c[2] = (double)r.q[11] + ((double)r.q[2] + (double)r.q[5]) / 3.0;
+}
+
+ERAY_HD uint64_t morton_key(const double* c, const double* lo, const double* hi) {
+    return spread3(morton_code(c[0], lo[0], hi[0])) << 2 | spread3(morton_code(c[1], lo[1], hi[1])) << 1 |
+           spread3(morton_code(c[2], lo[2], hi[2]));
+}
+
+// The tree of C culled faces.
+struct TreeLayout {
+    uint32_t C;
+    uint32_t full;   // F: levels 0 .. F are complete (C > 0)
+    uint32_t extra;  // nodes of level F that split once more
+    uint32_t nodes;
+    uint32_t depth;  // levels (0: no tree)
+};
+
+ERAY_HD TreeLayout tree_layout(uint32_t C) {
+    TreeLayout t{C, 0u, 0u, 0u, 0u};
+    if (!C) return t;
+    while ((C >> t.full) > kLeafFaces) ++t.full;
+    if ((C >> t.full) == kLeafFaces) t.extra = C - (kLeafFaces << t.full);
+    t.nodes = (2u << t.full) - 1u + 2u * t.extra;
+    t.depth = t.full + 1u + (t.extra ? 1u : 0u);
+    return t;
+}
+
+// Node j of the complete level L: its range [lo, lo + n) of the sorted order.
+ERAY_HD void node_range(uint32_t C, uint32_t L, uint32_t j, uint32_t& lo, uint32_t& n) {
+    lo = 0;
+    n = C;
+    for (uint32_t k = L; k-- > 0;) {
+        const uint32_t half = n / 2;
+        if ((j >> k) & 1u) {
+            lo += half;
+            n -= half;
+        } else {
+            n = half;
+        }
+    }
+}
+
+ERAY_HD uint32_t node_id(uint32_t L, uint32_t j) { return (1u << L) - 1u + j; }
+
+// The local ids of the children of the inner node j of level L starting at lo (left half first).
+ERAY_HD uint32_t first_child(const TreeLayout& t, uint32_t L, uint32_t j, uint32_t lo) {
+    return L < t.full ? node_id(L + 1, 2 * j) : node_id(t.full + 1, 0) + 2u * (lo - kLeafFaces * j);
+}
+
+// A node's real box and margins before rounding (temporary, one per node).
+struct NodeBounds {
+    double lo[3], hi[3], alpha, beta;
+};
+
+// c, h, alpha, beta rounded as the host builder rounds them: [c - h, c + h] holds [lo, hi].
+ERAY_HD void round_node(const NodeBounds& b, Node& n) {
+    for (int j = 0; j < 3; ++j) {
+        n.c[j] = (float)(0.5 * (b.lo[j] + b.hi[j]));
+        const double p = b.hi[j] - (double)n.c[j], q = (double)n.c[j] - b.lo[j];
+        n.h[j] = up(p > q ? p : q);
+    }
+    n.alpha = up(b.alpha);
+    n.beta = up(b.beta);
+}
+
+// The leaf of ids[0 .. count) (1 <= count <= kLeafFaces original indices, any order): sorted
+// ascending, copied with their records to slots [slot, slot + count), with the box of the faces'
+// vertices (a, a + e1, a + e2) in double.  alpha_beta[2 f], [2 f + 1]: the margins of face f.
+ERAY_HD void make_leaf(const uint32_t* ids, uint32_t count, const Hot* faces, const double* alpha_beta, uint32_t slot,
+                       Hot* hot, uint32_t* index, Node& node, NodeBounds& nb) {
+    uint32_t s[kLeafFaces];
+    for (uint32_t k = 0; k < kLeafFaces; ++k) s[k] = k < count ? ids[k] : 0xffffffffu;
+    for (uint32_t a = 1; a < kLeafFaces; ++a)  // (insertion sort of four words)
+        for (uint32_t b = a; b > 0 && s[b] < s[b - 1]; --b) {
+            const uint32_t t = s[b];
+            s[b] = s[b - 1];
+            s[b - 1] = t;
+        }
+    for (int j = 0; j < 3; ++j) {
+        nb.lo[j] = INFINITY;
+        nb.hi[j] = -INFINITY;
+    }
+    nb.alpha = 0.0;
+    nb.beta = 0.0;
+    for (uint32_t k = 0; k < kLeafFaces; ++k) {
+        if (k >= count) break;
+        const uint32_t f = s[k];
+        const Hot r = faces[f];
+        hot[slot + k] = r;
+        index[slot + k] = f;
+        for (int j = 0; j < 3; ++j) {
+            const double a = r.q[9 + j];
+            const double v[3] = {a, a + (double)r.q[j], a + (double)r.q[3 + j]};
+            for (int i = 0; i < 3; ++i) {
+                nb.lo[j] = v[i] < nb.lo[j] ? v[i] : nb.lo[j];
+                nb.hi[j] = v[i] > nb.hi[j] ? v[i] : nb.hi[j];
+            }
+        }
+        const double al = alpha_beta[2 * (size_t)f], be = alpha_beta[2 * (size_t)f + 1];
+        nb.alpha = al > nb.alpha ? al : nb.alpha;
+        nb.beta = be > nb.beta ? be : nb.beta;
+    }
+    round_node(nb, node);
+    node.left = kLeafBit | slot;
+    node.right = count;
+    node.min_index = s[0];
+    node.right_min = 0xffffffffu;
+}
+
+// The inner node over children l and r (global ids; their nodes and bounds are written): `left`
+// is the child with the smaller minimum index.
+ERAY_HD void make_inner(uint32_t l, uint32_t r, const Node* nodes, const NodeBounds* bounds, Node& node, NodeBounds& nb) {
+    const NodeBounds x = bounds[l], y = bounds[r];
+    for (int j = 0; j < 3; ++j) {
+        nb.lo[j] = x.lo[j] < y.lo[j] ? x.lo[j] : y.lo[j];
+        nb.hi[j] = x.hi[j] > y.hi[j] ? x.hi[j] : y.hi[j];
+    }
+    nb.alpha = x.alpha > y.alpha ? x.alpha : y.alpha;
+    nb.beta = x.beta > y.beta ? x.beta : y.beta;
+    round_node(nb, node);
+    const uint32_t lmin = nodes[l].min_index, rmin = nodes[r].min_index;
+    const bool left_first = lmin < rmin;
+    node.left = left_first ? l : r;
+    node.right = left_first ? r : l;
+    node.min_index = left_first ? lmin : rmin;
+    node.right_min = left_first ? rmin : lmin;
+}
+
+// One lane's work at `level` (0: the root) of the tree t, lane j: node j of a complete level, or
+// (level == t.full + 1) the two leaves under node j of level t.full when it splits once more.
+// Levels are run deepest first, so an inner node finds its children written.  sorted: the culled
+// faces in (key, index) order, each entry its original index + id_bias; slot0: the slot of
+// sorted[0]; nodes / bounds are the scene's, the tree's node k at node_base + k.
+ERAY_HD void level_node(const TreeLayout& t, uint32_t level, uint32_t j, const uint32_t* sorted, uint32_t id_bias,
+                        const Hot* faces, const double* alpha_beta, uint32_t node_base, uint32_t slot0, Node* nodes,
+                        NodeBounds* bounds, Hot* hot, uint32_t* index) {
+    const bool pairs = level == t.full + 1;
+    if (!t.C || (level > t.full && !(pairs && t.extra))) return;
+    const uint32_t L = pairs ? t.full : level;
+    if (j >= (1u << L)) return;
+    uint32_t lo, n;
+    node_range(t.C, L, j, lo, n);
+    uint32_t first[2] = {lo, lo + n / 2}, count[2] = {n, 0u}, id[2] = {node_base + node_id(L, j), 0u};
+    uint32_t leaves = n <= kLeafFaces ? 1u : 0u;
+    if (pairs) {
+        if (n <= kLeafFaces) return;
+        leaves = 2;
+        count[0] = n / 2;
+        count[1] = n - n / 2;
+        id[0] = node_base + first_child(t, L, j, lo);
+        id[1] = id[0] + 1;
+    }
+    for (uint32_t k = 0; k < 2; ++k) {
+        if (k >= leaves) break;
+        uint32_t f[kLeafFaces];
+        for (uint32_t q = 0; q < kLeafFaces; ++q) f[q] = q < count[k] ? sorted[first[k] + q] - id_bias : 0u;
+        Node nd;
+        NodeBounds nb;
+        make_leaf(f, count[k], faces, alpha_beta, slot0 + first[k], hot, index, nd, nb);
+        nodes[id[k]] = nd;
+        bounds[id[k]] = nb;
+    }
+    if (leaves) return;
+    const uint32_t c0 = node_base + first_child(t, L, j, lo);
+    Node nd;
+    NodeBounds nb;
+    make_inner(c0, c0 + 1, nodes, bounds, nd, nb);
+    nodes[id[0]] = nd;
+    bounds[id[0]] = nb;
+}
+
+}  // namespace accel
+}  // namespace eray

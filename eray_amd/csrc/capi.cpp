@@ -20,6 +20,8 @@
 
 #include "../../include/eray_hip.h"
 #include "accel_build.hpp"
+#include "accel_check.hpp"
+#include "accel_dev.hpp"
 #include "internal.hpp"
 #include "owners.hpp"
 #include "rays_args.hpp"
@@ -1333,6 +1335,51 @@ int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel
         }
         out.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
                            sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
+        ra.min_faces = min_faces;
+        ra.node_count = nodes.size();
+        ra.slot_count = leaf.size();
+        ra.valid = true;
+    }
+    out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = out;
+    return ERAY_OK;
+}
+
+// The same hierarchy built on the context's stream from the resident records (accel_dev.hip): one
+// round trip of 16 B of counters per covered object, no face record leaves the device.
+int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
+    if (int st = use_device(ctx)) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int st = sync_scene(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
+    RayAccel& ra = ctx->ray_accel;
+    ra.drop();
+    if (!min_faces) min_faces = 2 * kRayTile;
+    std::vector<AccelDevObject> covered;
+    eray_ray_accel_info out{};
+    uint32_t begin = 0;
+    for (size_t i = 0; i < ctx->objects.size(); ++i) {
+        const uint32_t n = ctx->objects[i].T;
+        if (n >= min_faces) {
+            covered.push_back(AccelDevObject{(uint32_t)i, begin, n});
+            ++out.objects;
+            out.faces += n;
+        }
+        begin += n;
+    }
+    if (out.objects) {
+        AccelDevInfo dev;
+        const char* refuse = nullptr;
+        HIP_TRY(ctx, accel_build_device(ctx->d_hot, covered, ctx->objects.size(), ra, ctx->stream, &dev, &refuse));
+        if (refuse) return set_error(ctx, ERAY_E_UNSUPPORTED, "eray_scene_build_ray_accel_device: %s", refuse);
+        out.nodes = dev.nodes;
+        out.max_depth = dev.max_depth;
+        out.unculled_faces = dev.unculled;
+        out.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
+                           sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
+        ra.min_faces = min_faces;
+        ra.node_count = dev.nodes;
+        ra.slot_count = out.faces;
         ra.valid = true;
     }
     out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2308,6 +2355,38 @@ extern "C" int eray_debug_set_bin_capacity(eray_ctx* ctx, uint64_t entries) {
     ctx->setup_key.clear();
     return ERAY_OK;
 }
+// The current hierarchy (of either builder) and the face records copied back and checked on the
+// host (accel_check.hpp).
+extern "C" int eray_debug_ray_accel_check(eray_ctx* ctx, char* msg, uint32_t cap) {
+    if (int st = use_device(ctx)) return st;
+    if (msg && cap) msg[0] = 0;
+    auto say = [&](int code, const char* text) {
+        if (msg && cap) std::snprintf(msg, cap, "%s", text);
+        return set_error(ctx, code, "eray_debug_ray_accel_check: %s", text);
+    };
+    const RayAccel& ra = ctx->ray_accel;
+    if (!ra.valid) return say(ERAY_E_INVALID_ARGUMENT, "the scene has no ray-query hierarchy");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t nobj = ctx->objects.size(), T = ctx->total_tris;
+    std::vector<uint32_t> sizes(nobj);
+    for (size_t i = 0; i < nobj; ++i) sizes[i] = ctx->objects[i].T;
+    std::vector<eray::accel::Hot> faces(T), hot(ra.slot_count);
+    std::vector<eray::accel::Object> objs(nobj);
+    std::vector<eray::accel::Node> nodes(ra.node_count);
+    std::vector<uint32_t> index(ra.slot_count);
+    if (T) HIP_TRY(ctx, hipMemcpy(faces.data(), ctx->d_hot, sizeof(TriHot) * T, hipMemcpyDeviceToHost));
+    if (nobj) HIP_TRY(ctx, hipMemcpy(objs.data(), ra.objs, sizeof(eray::accel::Object) * nobj, hipMemcpyDeviceToHost));
+    if (ra.node_count)
+        HIP_TRY(ctx, hipMemcpy(nodes.data(), ra.nodes, sizeof(eray::accel::Node) * ra.node_count, hipMemcpyDeviceToHost));
+    if (ra.slot_count) {
+        HIP_TRY(ctx, hipMemcpy(hot.data(), ra.hot, sizeof(eray::accel::Hot) * ra.slot_count, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(index.data(), ra.index, 4 * ra.slot_count, hipMemcpyDeviceToHost));
+    }
+    const char* bad = eray::accel::check(faces.data(), sizes.data(), nobj, ra.min_faces, objs.data(), nodes.data(), nodes.size(),
+                                         hot.data(), index.data(), index.size());
+    return bad ? say(ERAY_E_BUILD, bad) : ERAY_OK;
+}
+
 extern "C" uint64_t eray_debug_bin_capacity(const eray_ctx* ctx) { return ctx ? (uint64_t)ctx->bins.cap : 0u; }
 // Diagnostics: the frame setups' pair pass walks every (face, bin) pair of the faces' bin
 // rectangles (rect_pairs != 0) instead of the rectangles' rows (bins.hip bin_segments_kernel);

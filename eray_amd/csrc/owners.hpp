@@ -109,7 +109,7 @@ struct DeviceBuf : Buffer<T, hipFree> {
 };
 
 // The scene's ray-query hierarchy on the device (accel_walk.hpp; capi.cpp
-// eray_scene_build_ray_accel): per object its record, the nodes, the leaf-ordered copies of the
+// eray_scene_build_ray_accel and eray_scene_build_ray_accel_device): per object its record, the nodes, the leaf-ordered copies of the
 // face records (TriHot bytes) and their original indices.  `valid` falls with any geometry change
 // (a stale tree is never used); the memory is released by drop() or with the owner.
 struct RayAccel {
@@ -118,8 +118,13 @@ struct RayAccel {
     DeviceBuf<accel::Hot> hot;
     DeviceBuf<uint32_t> index;
     bool valid = false;
+    // what the last build covered (eray_debug_ray_accel_check): its min_faces, node and slot counts
+    uint32_t min_faces = 0;
+    size_t node_count = 0, slot_count = 0;
     void drop() {
         valid = false;
+        min_faces = 0;
+        node_count = slot_count = 0;
         (void)objs.release();
         (void)nodes.release();
         (void)hot.release();

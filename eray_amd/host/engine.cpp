@@ -316,11 +316,12 @@ Ray Ray::make(Vector3 start, Vector3 dir) {  // Ray::new (raycasting.rs:16-21): 
     return Ray{start, Vector3(dir.x / len, dir.y / len, dir.z / len)};
 }
 
-Engine::RayAccelInfo Engine::build_ray_accel(uint32_t min_faces) {
+Engine::RayAccelInfo Engine::build_ray_accel(uint32_t min_faces, bool on_device) {
     Device& d = Device::current();
     if (scene_.dirty_) upload();
     eray_ray_accel_info i{};
-    d.check(eray_scene_build_ray_accel(d.ctx(), min_faces, &i));
+    d.check(on_device ? eray_scene_build_ray_accel_device(d.ctx(), min_faces, &i)
+                      : eray_scene_build_ray_accel(d.ctx(), min_faces, &i));
     return RayAccelInfo{i.objects, i.max_depth, i.nodes, i.faces, i.unculled_faces, i.device_bytes, i.build_ms};
 }
 

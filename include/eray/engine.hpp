@@ -150,13 +150,14 @@ public:
     // A hierarchy for cast_rays over the objects of at least min_faces faces (0: the library's
     // default), built from the uploaded scene (eray_scene_build_ray_accel): the same hits, found
     // without scanning every face.  It lasts until the scene changes (scene() marks it changed:
-    // the next upload drops it) or drop_ray_accel.
+    // the next upload drops it) or drop_ray_accel.  on_device builds it on the GPU from the resident
+    // records (eray_scene_build_ray_accel_device) instead of on the host: the same hits either way.
     struct RayAccelInfo {
         uint32_t objects, max_depth;
         uint64_t nodes, faces, unculled_faces, device_bytes;
         float build_ms;
     };
-    RayAccelInfo build_ray_accel(uint32_t min_faces = 0);
+    RayAccelInfo build_ray_accel(uint32_t min_faces = 0, bool on_device = false);
     void drop_ray_accel();
     // The anti-aliasing jitter stream's key (eray_render_params::aa_seed).  The reference draws
     // from the OS-seeded thread_rng; a new Engine picks a random seed likewise, and fixing it

@@ -30,7 +30,7 @@
  *                           reaches_light engine.rs:218-228) fused with the PPM byte pack
  *   eray_cast_rays          lib/object.rs:58-81 (Object::intersects -> RaycastHit) and
  *                           lib/engine.rs:112-216 (Engine::cast_ray) for caller-supplied rays
- *   eray_scene_build_ray_accel  a hierarchy for eray_cast_rays that keeps object.rs:63-78's choice
+ *   eray_scene_build_ray_accel  (and _device: built on the GPU) a hierarchy for eray_cast_rays that keeps object.rs:63-78's choice
  *                           (the first passing face by index) and its bits
  *   eray_pack_ppm           lib/image.rs:48-74 + lib/color.rs:31-37 (save_as_ppm body bytes)
  *   eray_gather_rows        lib/engine.rs:85-98 + lib/image.rs:48-74 across GPUs (row tiles, RCCL)
@@ -446,6 +446,22 @@ typedef struct eray_ray_accel_info {   /*                                       
 } eray_ray_accel_info;
 int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info /* may be NULL */);
 int eray_scene_drop_ray_accel(eray_ctx* ctx);
+/* The same hierarchy (the same records, the same info fields, the same min_faces, invalidation and
+ * refusals; eray_scene_drop_ray_accel drops it, and a build of either kind replaces the other)
+ * built on the context's stream from the face records that are resident on the device: FP64
+ * margins one face per lane, a 63-bit Morton order of the centroids, a balanced split of that
+ * order with the host builder's arithmetic (the same node count and depth), leaves and boxes
+ * bottom-up.  No face record crosses the bus.  ONE device-to-host round trip exists: after the
+ * margin and key passes the host reads 16 bytes of counters per covered object (culled count,
+ * unculled count, a status word), which it needs to size the node array and lay out the levels.
+ * The call is synchronous like the host build: build_ms is host wall time from entry to the end of
+ * a final stream synchronisation, so the two figures compare.  Temporaries (keys, sort scratch,
+ * per-node double bounds) are released before it returns; device_bytes counts the persistent
+ * arrays only.  The split differs from the host build's (Morton order instead of the widest-axis
+ * median), so the trees differ while every query result is the same, bit for bit.  Present in
+ * builds that define ERAY_HAS_RAY_ACCEL_DEVICE. */
+#define ERAY_HAS_RAY_ACCEL_DEVICE 1
+int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info /* may be NULL */);
 
 /* ------------------------------------------------------------------ multi-GPU ----------- *
  * One process (one context) per GPU; a frame is split into row tiles and gathered on rank 0

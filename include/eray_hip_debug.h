@@ -85,6 +85,12 @@ int eray_debug_gather_replan(uint32_t cached, uint32_t plan_kind, uint64_t plan_
  * offset, row bytes, first packed row, 0). */
 int eray_debug_gather_layout(const int32_t* rects, uint32_t n, uint32_t height, uint32_t width, uint32_t band_rows,
                              uint32_t nranks, uint32_t rank, uint32_t* out);
+/* The scene's current ray-query hierarchy (of either builder) and the face records copied back
+ * and checked on the host (eray_amd/csrc/accel_check.hpp: permutation and byte copies, the
+ * unculled list, leaf order, min_index / right_min, boxes, alpha / beta / gamma, reachability,
+ * depth).  ERAY_OK, or an error with the first violated invariant in msg (at most cap bytes,
+ * may be null) and in eray_last_error. */
+int eray_debug_ray_accel_check(eray_ctx* ctx, char* msg, uint32_t cap);
 
 #ifdef __cplusplus
 }

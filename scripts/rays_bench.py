@@ -1,6 +1,7 @@
 """Times eray_cast_rays against the brute-force render of the same rays (diagnostics, GPU only).
 
     python scripts/rays_bench.py [--repeats 5] [--small-only] [--no-1m] [--out FILE.json]
+    python scripts/rays_bench.py --accel-build both [--repeats 5] [--no-1m] [--out FILE.json]
 
 Two cameras, main.rs's scene: C2 (1920x1080, cube.obj) and 3840x2160 over the 69,451-face
 stand-in mesh (bench.py's north-star scene).  The rays are the camera's own pixel-corner rays
@@ -20,6 +21,14 @@ Then the incoherent workload the hierarchy is for: 2^22 rays from the radius-3 s
 targets uniform in [-1, 1]^3 against the 69,451-face mesh with its true box (tiles against
 hierarchy), and 2^20 such rays against the 1M-face mesh (--no-1m skips it), with each mesh's build
 time and device bytes.  One JSON line per workload.  No GPU: the context fails to open.
+
+--accel-build {host,device,both} measures the hierarchy's builders instead (eray_scene_build_ray_accel
+and eray_scene_build_ray_accel_device): per scene — the 69,451-face mesh, the 1M-face mesh, 64
+objects of 1,024 faces — `repeats` builds of each chosen builder in one process, alternating after
+one untimed round (build_ms: host wall time of the whole call, final synchronisation included),
+and the query workloads (2^22 incoherent rays / 69k, 2^20 / 1M, the 3840x2160 camera's rays / 69k)
+timed by device events through each builder's tree, alternating likewise, the records compared
+byte for byte between the trees.
 """
 from __future__ import annotations
 
@@ -196,6 +205,93 @@ def bench_incoherent(name: str, mesh, nrays: int, repeats: int) -> dict:
             c.close()
 
 
+def bench_builders(name: str, objects: list, builders: list, workloads: dict, repeats: int) -> dict:
+    """Per builder a context holding `objects` ((mesh, lo, hi) each) and its hierarchy: build_ms of
+    `repeats` alternating builds, then each workload ({name: (n, 6) rays}) through each tree."""
+    stream = torch.cuda.Stream()
+    ctxs = {}
+    for b in builders:
+        c = capi.Context(0)
+        c.set_stream(stream.cuda_stream)
+        c.set_camera(capi.make_camera((0.0, 0.0, 5.0), (60.0, 60.0), 64, 1.0))
+        for mesh, lo, hi in objects:
+            c.add_object(*mesh, tuple(lo), tuple(hi))
+        ctxs[b] = c
+    out = {"scene": name, "objects": len(objects), "faces": int(sum(m[0].shape[0] for m, _, _ in objects)), "repeats": repeats}
+    bufs = []
+    try:
+        build_ms = {b: [] for b in builders}
+        info = {}
+        for rep in range(repeats + 1):  # round 0: warm-up
+            for b in builders:
+                info[b] = ctxs[b].build_ray_accel(1, device=(b == "device"))
+                if rep:
+                    build_ms[b].append(info[b]["build_ms"])
+        for b in builders:
+            out[f"build_{b}"] = summary(build_ms[b])
+            out[f"info_{b}"] = info[b]
+        if len(builders) == 2:
+            out["host_over_device_build"] = round(out["build_host"]["median_ms"] / out["build_device"]["median_ms"], 2)
+        for wname, rays_h in workloads.items():
+            n = rays_h.shape[0]
+            rays = ctxs[builders[0]].to_device(rays_h)
+            hit = ctxs[builders[0]].empty((n,), capi.HIT_DTYPE)
+            bufs += [rays, hit]
+            records = {}
+            times = {b: [] for b in builders}
+            for rep in range(repeats + 1):
+                for b in builders:
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record(stream)
+                    ctxs[b].cast_rays_device(rays.ptr, n, out_hit=hit.ptr, flags=capi.RAYS_NORMALIZE)
+                    t1.record(stream)
+                    t1.synchronize()
+                    if rep:
+                        times[b].append(t0.elapsed_time(t1))
+                    else:
+                        records[b] = hit.numpy().tobytes()
+            if len(set(records.values())) != 1:
+                raise AssertionError(f"{name}, {wname}: the two trees' records differ")
+            w = {"rays": n, **{f"query_{b}_tree": summary(times[b]) for b in builders}}
+            if len(builders) == 2:
+                w["device_over_host_tree"] = round(w["query_device_tree"]["median_ms"] / w["query_host_tree"]["median_ms"], 3)
+            out[wname] = w
+        return out
+    finally:
+        for a in bufs:
+            a.free()
+        for c in ctxs.values():
+            c.close()
+
+
+def bench_accel_build(which: str, repeats: int, no_1m: bool) -> list:
+    builders = ["host", "device"] if which == "both" else [which]
+    lines = []
+
+    def one(mesh):
+        p = mesh[0].reshape(-1, 3)
+        return (mesh, p.min(0), p.max(0))
+
+    m70 = generated_mesh(**meshgen.STANDIN_70K)
+    cam = camera_rays((0.0, 0.0, 5.0), fov_for(3840, 2160), 3840, 2160)
+    lines.append(bench_builders("69451 faces", [one(m70)], builders,
+                                {"incoherent_2^22": sphere_rays(1 << 22), "camera_3840x2160": cam}, repeats))
+    print(json.dumps(lines[-1]), flush=True)
+    many = []
+    for k in range(64):  # 64 displaced spheres of 1,024 faces on a 4 x 4 x 4 lattice
+        m = generated_mesh(1024, 100 + k)
+        c = np.float32([(k % 4 - 1.5) * 0.5, (k // 4 % 4 - 1.5) * 0.5, (k // 16 - 1.5) * 0.5])
+        pos = ((m[0].reshape(-1, 3, 3) * np.float32(0.2)) + c).reshape(-1, 9).astype(np.float32)
+        many.append(one((pos, m[1], m[2])))
+    lines.append(bench_builders("64 objects x 1024 faces", many, builders, {"incoherent_2^20": sphere_rays(1 << 20)}, repeats))
+    print(json.dumps(lines[-1]), flush=True)
+    if not no_1m:
+        lines.append(bench_builders("1M faces", [one(generated_mesh(**meshgen.SYNTH_1M))], builders,
+                                    {"incoherent_2^20": sphere_rays(1 << 20)}, repeats))
+        print(json.dumps(lines[-1]), flush=True)
+    return lines
+
+
 def generated_mesh(triangles: int, seed: int):
     v, n, t, F, _, _ = meshgen.displaced_sphere(triangles, seed)
     return (v[F].reshape(triangles, 9).astype(np.float32), n[F].reshape(triangles, 9).astype(np.float32),
@@ -207,8 +303,17 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--small-only", action="store_true", help="C2 only (skip the 69,451-face camera)")
     ap.add_argument("--no-1m", action="store_true", help="skip the 1M-face incoherent workload")
+    ap.add_argument("--accel-build", choices=("host", "device", "both"), default="",
+                    help="measure the hierarchy's builders and the queries through their trees instead")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.accel_build:
+        lines = bench_accel_build(a.accel_build, a.repeats, a.no_1m)
+        if a.out:
+            with open(a.out, "w") as f:
+                for ln in lines:
+                    f.write(json.dumps(ln) + "\n")
+        return
     lines = [bench("C2 1920x1080 cube", load_obj_file(os.path.join(ROOT, "objects", "cube.obj")), 1920, 1080, a.repeats)]
     print(json.dumps(lines[-1]), flush=True)
     if not a.small_only:
