@@ -108,7 +108,7 @@ ACCEL_DEV_HEADERS = ["accel_build.hpp", "accel_walk.hpp", "accel_margin.hpp", "a
 
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
-    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, accel_walk_main,
+    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, accel_walk_main,
     accel_dev_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
@@ -145,7 +145,8 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
                       ("test_host", os.path.join(ROOT, "tests", "cpp", "test_host.cpp")),
                       ("test_rays", os.path.join(ROOT, "tests", "cpp", "test_rays.cpp")),
                       ("test_accel", os.path.join(ROOT, "tests", "cpp", "test_accel.cpp")),
-                      ("test_accel_dev", os.path.join(ROOT, "tests", "cpp", "test_accel_dev.cpp"))):
+                      ("test_accel_dev", os.path.join(ROOT, "tests", "cpp", "test_accel_dev.cpp")),
+                      ("test_reach", os.path.join(ROOT, "tests", "cpp", "test_reach.cpp"))):
         exe = os.path.join(BIN_DIR, name)
         if force or not _newer(exe, [src, HOST_LIB] + headers):
             run([cxx, *flags, src, "-o", exe, "-L" + LIB_DIR, "-leray_host", *link])

@@ -130,6 +130,11 @@ class RaysParams(C.Structure):  # eray_rays_params
                 ("flags", C.c_uint32), ("out_hit", C.c_void_p), ("out_rgb", C.c_void_p)]
 
 
+class ReachParams(C.Structure):  # eray_reach_params
+    _fields_ = [("rays", C.c_void_p), ("targets", C.c_void_p), ("count", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("out", C.c_void_p)]
+
+
 class RayAccelInfo(C.Structure):  # eray_ray_accel_info
     _fields_ = [("objects", C.c_uint32), ("max_depth", C.c_uint32), ("nodes", C.c_uint64), ("faces", C.c_uint64),
                 ("unculled_faces", C.c_uint64), ("device_bytes", C.c_uint64), ("build_ms", C.c_float)]
@@ -197,6 +202,7 @@ SIGNATURES = {
     "eray_camera_size": (C.c_int, [C.POINTER(Camera), C.POINTER(_U), C.POINTER(_U)]),
     "eray_render": (C.c_int, [_P, C.POINTER(RenderParams)]),
     "eray_cast_rays": (C.c_int, [_P, C.POINTER(RaysParams)]),
+    "eray_rays_reach_light": (C.c_int, [_P, C.POINTER(ReachParams)]),
     "eray_scene_build_ray_accel": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
     "eray_scene_build_ray_accel_device": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
     "eray_scene_drop_ray_accel": (C.c_int, [_P]),
@@ -250,6 +256,10 @@ DEBUG_SIGNATURES = {
     "eray_debug_ray_accel_check": (C.c_int, [_P, C.c_char_p, _U]),
 }
 
+# Entry points a library selected by ERAY_LIB may predate (scripts/rays_bench.py --secondary runs the
+# parent commit's build): absent there, they stay unbound; the product library must have them all.
+_AB_OPTIONAL = {"eray_rays_reach_light"}
+
 _lib = None
 
 
@@ -281,6 +291,8 @@ def lib():
         _preload_hip_runtime()
         L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
         for name, (res, args) in SIGNATURES.items():
+            if os.environ.get("ERAY_LIB") and name in _AB_OPTIONAL and not hasattr(L, name):
+                continue  # (an older build under A/B: an entry point it predates)
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -646,6 +658,39 @@ class Context:
         if want_hits and want_rgb:
             return hits, rgb
         return hits if want_hits else rgb
+
+    def rays_reach_light_device(self, rays_ptr, targets_ptr, count, out_ptr, flags=0) -> None:
+        """eray_rays_reach_light on device buffers (count eray_ray and count x 3 f32 in, count
+        uint32 out): enqueued on the context's stream, nothing copied, nothing waited for."""
+        p = ReachParams(rays_ptr or None, targets_ptr or None, count, flags, 0, out_ptr or None)
+        self._check(lib().eray_rays_reach_light(self._h, C.byref(p)))
+
+    def rays_reach_light(self, rays, targets, normalize=False, brute_force=False) -> np.ndarray:
+        """Engine::reaches_light for caller-supplied shadow rays (eray_rays_reach_light).  rays:
+        (n, 6) float32 or RAY_DTYPE records; targets: (n, 3) float32, each ray's light position.
+        Returns n uint32 words: 1 the ray reaches its target, 0 an object blocks it."""
+        r = np.ascontiguousarray(rays)
+        r = (r.view(np.float32) if r.dtype == RAY_DTYPE else r.astype(np.float32, copy=False)).reshape(-1, 6)
+        t = np.ascontiguousarray(targets, np.float32).reshape(-1, 3)
+        n = r.shape[0]
+        if t.shape[0] != n:
+            raise ValueError("rays and targets disagree on the count")
+        flags = (RAYS_NORMALIZE if normalize else 0) | (RAYS_BRUTE_FORCE if brute_force else 0)
+        bufs = []
+        try:
+            d_rays = self.to_device(r if n else np.zeros((1, 6), np.float32))
+            bufs.append(d_rays)
+            d_tgt = self.to_device(t if n else np.zeros((1, 3), np.float32))
+            bufs.append(d_tgt)
+            d_out = self.empty((max(n, 1),), np.uint32)
+            bufs.append(d_out)
+            self.rays_reach_light_device(d_rays.ptr, d_tgt.ptr, n, d_out.ptr, flags)
+            self.synchronize()
+            out = d_out.numpy()[:n]
+        finally:
+            for a in bufs:
+                a.free()
+        return out
 
     def render_frames(self, frames, image_width, image_height, row0=0, rows=None, out_rgb=None,
                       out_ppm=None, out_face=None, flags=RENDER_DEFAULT, timed=False, prepare_only=False,

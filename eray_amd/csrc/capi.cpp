@@ -1278,6 +1278,36 @@ int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* rp) {
     return ERAY_OK;
 }
 
+// Engine::reaches_light for caller-supplied shadow rays (rays.hip reach_kernel): one kernel on the
+// context's stream like eray_cast_rays, so a call on an uploaded scene can be captured.
+int eray_rays_reach_light(eray_ctx* ctx, const eray_reach_params* rp) {
+    if (int st = use_device(ctx)) return st;
+    const char* why = "";
+    if (int st = eray::check_reach_params(rp, &why)) return set_error(ctx, st, "eray_rays_reach_light: %s", why);
+    if (!rp->count) return ERAY_OK;
+    if (int st = sync_scene(ctx)) return st;
+    ReachBatch b;
+    std::memset(&b, 0, sizeof b);
+    FrameParams& p = b.f;
+    p.nframes = 1;
+    p.tris = ctx->d_hot;
+    p.objects = ctx->d_objs;
+    p.nobj = (uint32_t)ctx->objects.size();
+    p.total_tris = ctx->total_tris;
+    b.rays = reinterpret_cast<const RayIn*>(rp->rays);
+    b.targets = rp->targets;
+    b.count = rp->count;
+    b.normalize = (rp->flags & ERAY_RAYS_NORMALIZE) ? 1u : 0u;
+    b.brute = (rp->flags & ERAY_RAYS_BRUTE_FORCE) ? 1u : 0u;
+    b.out = rp->out;
+    RayAccelView av{nullptr, nullptr, nullptr, nullptr};
+    if (ctx->ray_accel.valid)  // (never a stale tree: every geometry change clears `valid`)
+        av = RayAccelView{ctx->ray_accel.objs, ctx->ray_accel.nodes,
+                          reinterpret_cast<const TriHot*>((const eray::accel::Hot*)ctx->ray_accel.hot), ctx->ray_accel.index};
+    HIP_TRY(ctx, launch_reach_light(b, av, ctx->stream));
+    return ERAY_OK;
+}
+
 // The ray-query hierarchy (accel_build.hpp): built on the host from the device's own TriHot
 // records — the bits the kernels test — and uploaded; synchronous.
 int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {

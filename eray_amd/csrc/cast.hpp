@@ -4,6 +4,13 @@
 // camera's centre, the hit's Level (Material::get), reaches_light, a light's shading and the
 // depth-first walk that is cast_ray(ray, 0).sum().  Same f32 operations, in the same order, as the
 // Rust source each function cites (compile with -ffp-contract=off).
+//
+// How an object's first face is found is the caller's: surface, reaches_light and walk take a
+// face finder, a callable (oi, ob, o, d, u, v, t) -> int that returns Object::intersects' face of
+// object oi (geometry ob) for Ray(o, d), -1 for none, with that face's u, v, t.  ScanFaces is the
+// per-lane scan (first_face) that trace.hip and rays.hip's rays_kernel use through the overloads
+// without a finder; rays_accel_kernel and reach_kernel pass one that goes through the ray-query
+// hierarchy.  Every finder returns the same face and the same bits.
 #pragma once
 
 #include "device_math.hpp"
@@ -45,6 +52,15 @@ __device__ __forceinline__ int first_face(const TriHot* tris, const ObjGeom& ob,
         if (exact_test(r[f], o, d, u, v, t)) return (int)f;
     return -1;
 }
+
+// The default face finder: every face of the object in index order, through the lane's own loads.
+struct ScanFaces {
+    const TriHot* tris;
+    const uint64_t* live;
+    __device__ __forceinline__ int operator()(uint32_t, const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t) const {
+        return first_face(tris, ob, o, d, u, v, t, live);
+    }
+};
 
 // One level of cast_ray: the closest object's hit and the Material::get values at it.
 struct Level {
@@ -114,15 +130,16 @@ __device__ void fill_level(const FrameParams& p, f3 o, f3 d, const Hit& h, Level
 }
 
 // The closest object's first hit along Ray(o, d) (engine.rs:116-126) and its Level; false on a
-// miss.  Every face of every object (reflected rays; camera rays of small scenes via `live`).
-__device__ bool surface(const FrameParams& p, f3 o, f3 d, Level& L, int32_t* face_out, const uint64_t* live) {
+// miss.  `find` gives each object's face (reflected rays; camera rays of small scenes via `live`).
+template <class Find>
+__device__ bool surface(const FrameParams& p, f3 o, f3 d, Level& L, int32_t* face_out, const Find& find) {
     const f3 C = mk3(p.cx, p.cy, p.cz);
     Hit h;
     h.f = -1;
     for (uint32_t oi = 0; oi < p.nobj; ++oi) {
         const ObjGeom ob = p.objects[oi].g;
         float u, v, t;
-        const int f = first_face(p.tris, ob, o, d, u, v, t, live);
+        const int f = find(oi, ob, o, d, u, v, t);
         closer(h, oi, f, u, v, t, o, d, C);
     }
     if (h.f < 0) return false;
@@ -130,14 +147,18 @@ __device__ bool surface(const FrameParams& p, f3 o, f3 d, Level& L, int32_t* fac
     fill_level(p, o, d, h, L);
     return true;
 }
+__device__ bool surface(const FrameParams& p, f3 o, f3 d, Level& L, int32_t* face_out, const uint64_t* live) {
+    return surface(p, o, d, L, face_out, ScanFaces{p.tris, live});
+}
 
 // Engine::reaches_light (engine.rs:218-228): the FIRST object with any hit decides.
-__device__ bool reaches_light(const FrameParams& p, f3 S, f3 sd, f3 Lp) {
+template <class Find>
+__device__ bool reaches_light(const FrameParams& p, f3 S, f3 sd, f3 Lp, const Find& find) {
     const float dist = len(sub(Lp, S));
     for (uint32_t oi = 0; oi < p.nobj; ++oi) {
         const ObjGeom ob = p.objects[oi].g;
         float u, v, t;
-        if (first_face(p.tris, ob, S, sd, u, v, t, nullptr) >= 0) return len(sub(add(S, mul(sd, t)), S)) > dist;
+        if (find(oi, ob, S, sd, u, v, t) >= 0) return len(sub(add(S, mul(sd, t)), S)) > dist;
     }
     return true;
 }
@@ -161,8 +182,8 @@ __device__ __forceinline__ rgb shade(const Level& L, const LightDesc& Ld) {
 // Engine::cast_ray(ray, 0).sum() (engine.rs:112-216, color.rs:82-87) as a depth-first walk from
 // the first level's hit `first`.  kBounce false: no reflection levels (bounces == 0), so the walk
 // needs no per-depth frames.
-template <bool kBounce>
-__device__ rgb walk(const FrameParams& p, const Level& first) {
+template <bool kBounce, class Find>
+__device__ rgb walk(const FrameParams& p, const Level& first, const Find& find) {
     Level st[kBounce ? kMaxBounces + 1 : 1];
     st[0] = first;
     bool any = false;
@@ -182,10 +203,10 @@ __device__ rgb walk(const FrameParams& p, const Level& first) {
             if (Ld.variant == 1) continue;  // ambient lights come after the loop
             const f3 Lp = mk3(Ld.pos[0], Ld.pos[1], Ld.pos[2]);
             const f3 S = add(L.P, mul(L.N, 0.1f));
-            if (reaches_light(p, S, normalize(sub(Lp, L.P)), Lp)) emit(shade(L, Ld), depth);
+            if (reaches_light(p, S, normalize(sub(Lp, L.P)), Lp, find)) emit(shade(L, Ld), depth);
             if (kBounce && (uint32_t)depth < p.bounces && L.refl != 0.0f) {  // engine.rs:181-191
                 const f3 rd = normalize(sub(L.d, mul(mul(L.N, 2.0f), dot0(L.d, L.N))));
-                if (surface(p, S, rd, st[depth + 1], nullptr, nullptr))
+                if (surface(p, S, rd, st[depth + 1], nullptr, find))
                     ++depth;
                 else
                     emit(miss, depth + 1);
@@ -202,6 +223,10 @@ __device__ rgb walk(const FrameParams& p, const Level& first) {
         }
     }
     return acc;
+}
+template <bool kBounce>
+__device__ rgb walk(const FrameParams& p, const Level& first) {
+    return walk<kBounce>(p, first, ScanFaces{p.tris, nullptr});
 }
 
 // The miss colour (engine.rs:211-213): a ray that hits nothing returns vec![it].

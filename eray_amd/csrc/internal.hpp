@@ -452,6 +452,18 @@ struct RayAccelView {
     const uint32_t* index;
 };
 hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_t s);
+// eray_rays_reach_light: Engine::reaches_light per caller-supplied shadow ray.  `f` carries the
+// triangle records, the descriptors and the object count, the rest zero.
+struct ReachBatch {
+    FrameParams f;
+    const RayIn* rays;
+    const float* targets;  // count x 3: the light's position of each ray
+    uint64_t count;
+    uint32_t normalize;  // dir goes through Ray::new
+    uint32_t brute;      // per-lane first_face, no tiles, no hierarchy (ERAY_RAYS_BRUTE_FORCE)
+    uint32_t* out;       // count words: 1 reaches, 0 blocked
+};
+hipError_t launch_reach_light(const ReachBatch& b, const RayAccelView& a, hipStream_t s);
 
 // ------------------------------------------------------------- screen bins (bins.hip)
 // Device arrays of the binned objects' screen bins for one layout (camera size, row phase, the

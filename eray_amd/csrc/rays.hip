@@ -1,5 +1,6 @@
 // rays.hip — ray queries on gfx950: Object<Built>::intersects (object.rs:58-81) and
-// Engine::cast_ray (engine.rs:112-216) for a batch of caller-supplied rays (eray_cast_rays).
+// Engine::cast_ray (engine.rs:112-216) for a batch of caller-supplied rays (eray_cast_rays), and
+// Engine::reaches_light (engine.rs:218-228) for caller-supplied shadow rays (eray_rays_reach_light).
 //
 // The frame kernel and the general tracer make their own rays from the camera; here the rays
 // come from the caller and go anywhere, so nothing camera-shaped (culling records, pixel
@@ -31,7 +32,17 @@
 // a byte copy of the same record, i.e. the scan's bits.  Rays the margin proof does not cover scan
 // per lane (first_face); objects without a hierarchy keep the tiles, and since the choice is per
 // object (wave- and workgroup-uniform) the tiles' barriers stay uniform.  out_rgb's shadow and
-// reflected rays keep cast.hpp's per-lane scan either way (cast.hpp is shared with trace.hip).
+// reflected rays search the objects that have a hierarchy through it as well: cast.hpp's walk takes
+// a face finder, and rays_accel_kernel passes AccelFaces, which holds the RayAccelView and the
+// lane's stack column (empty again once the primary walk has returned, so the secondary walks
+// reuse it: no more LDS, no scratch).  Objects without a hierarchy are scanned per lane by those
+// rays — they run inside the walk's divergent loop, where no workgroup barrier can stand.  Same
+// faces, same u, v, t, same colours.
+//
+// eray_rays_reach_light (reach_kernel) is Engine::reaches_light (engine.rs:218-228) for shadow
+// rays the caller supplies, one lane per ray and one dword out, in the same three forms: the
+// hierarchy, the tiles (a lane that an earlier object has decided passes inbox == false and keeps
+// the barriers uniform), and the per-lane scan.
 //
 // ERAY_RAYS_BRUTE_FORCE is the plain form: every lane walks every face through its own loads
 // (cast.hpp first_face), no tiles, no workgroup-level skips — the same exact_test on the same
@@ -107,8 +118,9 @@ __device__ __forceinline__ void hit_record(const FrameParams& p, f3 o, f3 d, con
 }
 
 // A finished ray's outputs: its hit record and, with kRgb, cast_ray(ray, 0).sum() from that hit.
-template <bool kRgb, bool kBounce>
-__device__ __forceinline__ void store_ray(const RayBatch& b, uint64_t i, f3 o, f3 d, const Hit& h) {
+// `find`: the face finder of the shadow and reflected rays (cast.hpp).
+template <bool kRgb, bool kBounce, class Find>
+__device__ __forceinline__ void store_ray(const RayBatch& b, uint64_t i, f3 o, f3 d, const Hit& h, const Find& find) {
     const FrameParams& p = b.f;
     if (b.out_hit) {
         uint4 q[3];
@@ -123,7 +135,7 @@ __device__ __forceinline__ void store_ray(const RayBatch& b, uint64_t i, f3 o, f
         if (h.f >= 0) {
             Level L;
             fill_level(p, o, d, h, L);
-            c = walk<kBounce>(p, L);
+            c = walk<kBounce>(p, L, find);
         }
         float* dst = b.out_rgb + 3 * i;
         dst[0] = c.r;
@@ -133,14 +145,14 @@ __device__ __forceinline__ void store_ray(const RayBatch& b, uint64_t i, f3 o, f
 }
 
 // This lane's ray from the batch (dead lanes: a harmless ray), as rays_kernel loads its own.
-__device__ __forceinline__ void load_ray(const RayBatch& b, uint64_t i, bool live, f3& o, f3& d) {
+__device__ __forceinline__ void load_ray(const RayIn* rays, uint32_t norm, uint64_t i, bool live, f3& o, f3& d) {
     o = mk3(0.0f, 0.0f, 0.0f);
     d = mk3(0.0f, 0.0f, -1.0f);
     if (live) {
-        const RayIn r = b.rays[i];
+        const RayIn r = rays[i];
         o = mk3(r.start[0], r.start[1], r.start[2]);
         d = mk3(r.dir[0], r.dir[1], r.dir[2]);
-        if (b.normalize) d = normalize(d);  // Ray::new (raycasting.rs:16-21, vector.rs:150-158)
+        if (norm) d = normalize(d);  // Ray::new (raycasting.rs:16-21, vector.rs:150-158)
     }
 }
 
@@ -176,7 +188,7 @@ __global__ void __launch_bounds__(256) rays_kernel(RayBatch b) {
             }
             closer(h, oi, f, u, v, t, o, d, C);
         }
-        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h);
+        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h, ScanFaces{p.tris, nullptr});
     }
 }
 
@@ -191,7 +203,7 @@ struct LaneStack {
 
 // An object's first passing face through its hierarchy (accel_walk.hpp) for a ray that passed its
 // box; rays the margin proof does not cover scan per lane.
-__device__ __forceinline__ int accel_object_face(const RayBatch& b, const RayAccelView& a, const accel::Object& ao,
+__device__ __forceinline__ int accel_object_face(const TriHot* tris, const RayAccelView& a, const accel::Object& ao,
                                                  const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t,
                                                  uint32_t* stack) {
     const float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z};
@@ -205,8 +217,26 @@ __device__ __forceinline__ int accel_object_face(const RayBatch& b, const RayAcc
         t = tt;
         return true;
     });
-    return f == accel::kAccelFallback ? first_face(b.f.tris, ob, o, d, u, v, t, nullptr) : f;
+    return f == accel::kAccelFallback ? first_face(tris, ob, o, d, u, v, t, nullptr) : f;
 }
+
+// The face finder (cast.hpp) of out_rgb's shadow and reflected rays in a scene with a hierarchy:
+// an object that has one is searched as the primary ray searches it (the box, the unculled faces,
+// the walk; fallback rays scan), any other by the per-lane scan — these rays run inside the
+// divergent walk of cast.hpp, where the tiles' barriers cannot be reached by the whole workgroup.
+// `stack` is the lane's column of s_stack: the primary walk has returned, so it is empty, and
+// every search leaves it empty again.
+struct AccelFaces {
+    const TriHot* tris;
+    const RayAccelView& a;
+    uint32_t* stack;
+    __device__ __forceinline__ int operator()(uint32_t oi, const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t) const {
+        const accel::Object ao = load_const(&a.objs[oi], 0);
+        if (!ao.has) return first_face(tris, ob, o, d, u, v, t, nullptr);
+        if (!bbox_hit(ob, o, d)) return -1;
+        return accel_object_face(tris, a, ao, ob, o, d, u, v, t, stack);
+    }
+};
 
 // rays_kernel's tiled form for a scene with a ray-query hierarchy: objects that have one go
 // through it, the others through the tiles (the choice is per object, so every barrier of
@@ -224,7 +254,7 @@ __global__ void __launch_bounds__(256) rays_accel_kernel(RayBatch b, RayAccelVie
         const uint64_t i = base + threadIdx.x;
         const bool live = i < b.count;
         f3 o, d;
-        load_ray(b, i, live, o, d);
+        load_ray(b.rays, b.normalize, i, live, o, d);
         Hit h;
         h.f = -1;
         for (uint32_t oi = o0; oi < o1; ++oi) {  // scene order (engine.rs:116)
@@ -233,21 +263,71 @@ __global__ void __launch_bounds__(256) rays_accel_kernel(RayBatch b, RayAccelVie
             float u, v, t;
             int f = -1;
             if (ao.has) {  // (workgroup-uniform)
-                if (live && bbox_hit(ob, o, d)) f = accel_object_face(b, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
+                if (live && bbox_hit(ob, o, d))
+                    f = accel_object_face(p.tris, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
             } else {
                 f = tile_first_face(p.tris, ob, live && bbox_hit(ob, o, d), o, d, u, v, t, s_tile, s_need, phase);
             }
             closer(h, oi, f, u, v, t, o, d, C);
         }
-        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h);
+        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h, AccelFaces{p.tris, a, &s_stack[0][threadIdx.x]});
+    }
+}
+
+// eray_rays_reach_light: Engine::reaches_light (engine.rs:218-228) per caller-supplied shadow ray,
+// one lane per ray, one dword out.  The objects go in scene order and the first one with a hit
+// decides; a lane that an earlier object has decided stays in the loop with inbox == false, so the
+// tiles' barriers stay workgroup-uniform.  kAccel: objects that have a hierarchy go through it
+// (the lane's stack column in LDS); without it the kernel carries no stack and keeps the tiled
+// kernel's occupancy.  b.brute is cast.hpp's reaches_light with the per-lane scan.
+template <bool kAccel>
+__global__ void __launch_bounds__(256) reach_kernel(ReachBatch b, RayAccelView a) {
+    __shared__ TriHot s_tile[kRayTile];
+    __shared__ uint32_t s_need[2][4];
+    __shared__ uint32_t s_stack[kAccel ? accel::kStackDepth : 1][256];
+    const FrameParams& p = b.f;
+    uint32_t phase = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 256u; base < b.count; base += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = base + threadIdx.x;
+        const bool live = i < b.count;
+        f3 o, d;
+        load_ray(b.rays, b.normalize, i, live, o, d);
+        f3 Lp = o;
+        if (live) Lp = mk3(b.targets[3 * i], b.targets[3 * i + 1], b.targets[3 * i + 2]);
+        if (b.brute) {  // (workgroup-uniform)
+            if (live) b.out[i] = reaches_light(p, o, d, Lp, ScanFaces{p.tris, nullptr}) ? 1u : 0u;
+            continue;
+        }
+        const float dist = len(sub(Lp, o));
+        bool decided = false, reach = true;
+        for (uint32_t oi = 0; oi < p.nobj; ++oi) {  // scene order (engine.rs:220)
+            const ObjGeom ob = load_const(&p.objects[oi].g, 0);
+            const bool inbox = live && !decided && bbox_hit(ob, o, d);
+            float u, v, t;
+            int f = -1;
+            bool tiles = true;
+            if constexpr (kAccel) {
+                const accel::Object ao = load_const(&a.objs[oi], 0);
+                if (ao.has) {  // (workgroup-uniform)
+                    tiles = false;
+                    if (inbox) f = accel_object_face(p.tris, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
+                }
+            }
+            if (tiles) f = tile_first_face(p.tris, ob, inbox, o, d, u, v, t, s_tile, s_need, phase);
+            if (f >= 0) {
+                decided = true;
+                reach = len(sub(add(o, mul(d, t)), o)) > dist;
+            }
+        }
+        if (live) b.out[i] = reach ? 1u : 0u;
     }
 }
 
 }  // namespace
 
-hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_t s) {
-    if (!b.count) return hipSuccess;
-    if (!b.rays || (!b.out_hit && !b.out_rgb)) return hipErrorInvalidValue;
+namespace {
+// a workgroup per 256 rays, at most the 8 per CU the registers and the 12-KB tile allow at once
+dim3 ray_grid(uint64_t count) {
     static const uint32_t cus = [] {
         int dev = 0, n = 0;
         return (hipGetDevice(&dev) == hipSuccess &&
@@ -255,9 +335,24 @@ hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_
                    ? (uint32_t)n
                    : 256u;
     }();
-    // a workgroup per 256 rays, at most the 8 per CU the registers and the 12-KB tile allow at once
-    const uint64_t blocks = (b.count + 255u) / 256u, cap = 8ull * cus;
-    const dim3 grid((uint32_t)(blocks < cap ? blocks : cap));
+    const uint64_t blocks = (count + 255u) / 256u, cap = 8ull * cus;
+    return dim3((uint32_t)(blocks < cap ? blocks : cap));
+}
+}  // namespace
+
+hipError_t launch_reach_light(const ReachBatch& b, const RayAccelView& a, hipStream_t s) {
+    if (!b.count) return hipSuccess;
+    if (!b.rays || !b.targets || !b.out) return hipErrorInvalidValue;
+    const dim3 grid = ray_grid(b.count);
+    if (a.objs && !b.brute) hipLaunchKernelGGL((reach_kernel<true>), grid, dim3(256), 0, s, b, a);
+    else hipLaunchKernelGGL((reach_kernel<false>), grid, dim3(256), 0, s, b, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_t s) {
+    if (!b.count) return hipSuccess;
+    if (!b.rays || (!b.out_hit && !b.out_rgb)) return hipErrorInvalidValue;
+    const dim3 grid = ray_grid(b.count);
     if (a.objs && !b.brute) {  // (the hierarchy's stack: 32 KB of LDS more, 3 workgroups per CU resident)
         if (!b.out_rgb) hipLaunchKernelGGL((rays_accel_kernel<false, false>), grid, dim3(256), 0, s, b, a);
         else if (b.f.bounces) hipLaunchKernelGGL((rays_accel_kernel<true, true>), grid, dim3(256), 0, s, b, a);

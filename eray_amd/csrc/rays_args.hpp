@@ -1,6 +1,7 @@
-// rays_args.hpp — eray_cast_rays' argument validation (include/eray_hip.h states the rules): plain
-// host code with no HIP call, so capi.cpp and a stand-alone checker (tests/cpp/rays_args_main.cpp,
-// built with the host sanitizers) share it.
+// rays_args.hpp — eray_cast_rays' and eray_rays_reach_light's argument validation
+// (include/eray_hip.h states the rules): plain host code with no HIP call, so capi.cpp and the
+// stand-alone checkers (tests/cpp/rays_args_main.cpp, tests/cpp/reach_args_main.cpp, built with
+// the host sanitizers) share it.
 #pragma once
 
 #include <stddef.h>
@@ -28,6 +29,20 @@ inline int check_rays_params(const eray_rays_params* rp, size_t nobj, const char
         return *why = "object is neither -1 nor an object of the scene", ERAY_E_INVALID_ARGUMENT;
     if (rp->count && !rp->rays) return *why = "rays is null", ERAY_E_INVALID_ARGUMENT;
     if (reinterpret_cast<uintptr_t>(rp->out_hit) & 15u) return *why = "out_hit is not 16-byte aligned", ERAY_E_INVALID_ARGUMENT;
+    return ERAY_OK;
+}
+
+// The same for eray_rays_reach_light: ERAY_OK when `rp` can be enqueued (count == 0 included).
+inline int check_reach_params(const eray_reach_params* rp, const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!rp) return *why = "params is null", ERAY_E_INVALID_ARGUMENT;
+    if (rp->flags & ~(ERAY_RAYS_NORMALIZE | ERAY_RAYS_BRUTE_FORCE)) return *why = "unknown ray flags", ERAY_E_INVALID_ARGUMENT;
+    if (rp->reserved) return *why = "reserved is not 0", ERAY_E_INVALID_ARGUMENT;
+    if (rp->count && !rp->rays) return *why = "rays is null", ERAY_E_INVALID_ARGUMENT;
+    if (rp->count && !rp->targets) return *why = "targets is null", ERAY_E_INVALID_ARGUMENT;
+    if (rp->count && !rp->out) return *why = "out is null", ERAY_E_INVALID_ARGUMENT;
     return ERAY_OK;
 }
 

@@ -364,6 +364,35 @@ std::vector<std::optional<RaycastHit>> Engine::cast_rays(const std::vector<Ray>&
     return out;
 }
 
+std::vector<bool> Engine::reaches_light(const std::vector<Ray>& rays, const std::vector<Vector3>& targets) {
+    if (rays.size() != targets.size()) throw Failure(ERAY_E_INVALID_ARGUMENT, "reaches_light: one target per ray");
+    Device& d = Device::current();
+    if (scene_.dirty_) upload();
+    std::vector<bool> out(rays.size());
+    if (rays.empty()) return out;
+    std::vector<eray_ray> in(rays.size());
+    std::vector<float> tg(3 * rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) {
+        in[i] = eray_ray{{rays[i].start.x, rays[i].start.y, rays[i].start.z}, {rays[i].dir.x, rays[i].dir.y, rays[i].dir.z}};
+        tg[3 * i] = targets[i].x;
+        tg[3 * i + 1] = targets[i].y;
+        tg[3 * i + 2] = targets[i].z;
+    }
+    DeviceBuffer d_in(in.size() * sizeof(eray_ray)), d_tg(tg.size() * sizeof(float)), d_out(in.size() * sizeof(uint32_t));
+    d.check(eray_copy_to_device(d.ctx(), d_in.data(), in.data(), in.size() * sizeof(eray_ray)));
+    d.check(eray_copy_to_device(d.ctx(), d_tg.data(), tg.data(), tg.size() * sizeof(float)));
+    eray_reach_params p{};
+    p.rays = static_cast<const eray_ray*>(d_in.data());
+    p.targets = static_cast<const float*>(d_tg.data());
+    p.count = in.size();
+    p.out = static_cast<uint32_t*>(d_out.data());
+    d.check(eray_rays_reach_light(d.ctx(), &p));
+    std::vector<uint32_t> words(in.size());
+    d.check(eray_copy_to_host(d.ctx(), words.data(), d_out.data(), words.size() * sizeof(uint32_t)));
+    for (size_t i = 0; i < words.size(); ++i) out[i] = words[i] != 0;
+    return out;
+}
+
 const Image<Color>& Engine::render_to_path(const std::string& path) {  // engine.rs:86-98
     render();
     save_as_ppm(image_, path);

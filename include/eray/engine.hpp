@@ -147,6 +147,11 @@ public:
     // scene's closest object as cast_ray selects it (by the camera's centre, engine.rs:116-126),
     // k >= 0 Object k alone; nullopt is a miss
     std::vector<std::optional<RaycastHit>> cast_rays(const std::vector<Ray>& rays, int object = -1);
+    // engine.rs:218-228 Engine::reaches_light for each shadow ray and its light position, on the
+    // GPU (eray_rays_reach_light): true unless the first object in scene order that the ray hits
+    // is hit no farther from the ray's start than the target lies.  cast_ray's own shadow ray of a
+    // hit at P with normal N is Ray::make(P + N * 0.1, L - P) with target L (engine.rs:136-141).
+    std::vector<bool> reaches_light(const std::vector<Ray>& rays, const std::vector<Vector3>& targets);
     // A hierarchy for cast_rays over the objects of at least min_faces faces (0: the library's
     // default), built from the uploaded scene (eray_scene_build_ray_accel): the same hits, found
     // without scanning every face.  It lasts until the scene changes (scene() marks it changed:

@@ -32,6 +32,7 @@
  *                           lib/engine.rs:112-216 (Engine::cast_ray) for caller-supplied rays
  *   eray_scene_build_ray_accel  (and _device: built on the GPU) a hierarchy for eray_cast_rays that keeps object.rs:63-78's choice
  *                           (the first passing face by index) and its bits
+ *   eray_rays_reach_light   lib/engine.rs:218-228 (Engine::reaches_light) for caller-supplied shadow rays
  *   eray_pack_ppm           lib/image.rs:48-74 + lib/color.rs:31-37 (save_as_ppm body bytes)
  *   eray_gather_rows        lib/engine.rs:85-98 + lib/image.rs:48-74 across GPUs (row tiles, RCCL)
  *   eray_gather_frames      the same for a batch of frames (a frame ring), optionally sync-free
@@ -418,8 +419,12 @@ typedef struct eray_rays_params {   /*                                          
  * call after a scene change uploads it), so it can be captured into a HIP graph.  A miss scans
  * every face of every object whose box the ray passes, unless the scene has a ray-query hierarchy
  * (eray_scene_build_ray_accel below): objects that have one are then searched through it, with
- * the same records as results, bit for bit.  ERAY_RAYS_BRUTE_FORCE stays the per-ray scan.  The
- * shadow and reflected rays of out_rgb scan per ray either way. */
+ * the same records as results, bit for bit.  ERAY_RAYS_BRUTE_FORCE stays the per-ray scan.  In
+ * builds that define ERAY_HAS_RAY_ACCEL_SECONDARY the shadow and reflected rays of out_rgb search
+ * the objects that have a hierarchy through it as well (the box, the unculled faces, the walk),
+ * with the same colours, bit for bit; objects without one, and every object without a hierarchy
+ * or with ERAY_RAYS_BRUTE_FORCE, are scanned per ray by those rays. */
+#define ERAY_HAS_RAY_ACCEL_SECONDARY 1   /* out_rgb's shadow and reflected rays use the hierarchy */
 int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* params);
 
 /* A hierarchy for eray_cast_rays over the objects of at least min_faces faces (0: 512, two of the
@@ -462,6 +467,34 @@ int eray_scene_drop_ray_accel(eray_ctx* ctx);
  * builds that define ERAY_HAS_RAY_ACCEL_DEVICE. */
 #define ERAY_HAS_RAY_ACCEL_DEVICE 1
 int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info /* may be NULL */);
+
+/* Engine::reaches_light (engine.rs:218-228) for shadow rays the caller supplies: "does this point
+ * see that point" for light baking, visibility probes and a caller's own shading.  Per ray i:
+ * dist = |targets[i] - start|; the objects are taken in scene order and the FIRST object whose
+ * Object::intersects (the box, then the first face by index, as eray_cast_rays with that object)
+ * returns a hit decides: out[i] = |position - start| > dist ? 1 : 0, with position = start + dir * t
+ * of that hit — a later object that is nearer does not matter, as in the reference; no object
+ * hit: 1.  The lengths are Vector::len in f32 (the fold from 0).  dir is used as given, or goes
+ * through Ray::new with ERAY_RAYS_NORMALIZE.  cast_ray forms its shadow ray from a hit with
+ * position P and normal N and a point light at L as start = P + N * 0.1, dir = normalize(L - P)
+ * (from P, not from start), target = L (engine.rs:133-141); with an eray_ray_hit's position and
+ * normal a caller reproduces cast_ray's visibility term exactly.  Objects that have a ray-query
+ * hierarchy are searched through it, the others through the LDS tiles; ERAY_RAYS_BRUTE_FORCE is
+ * the per-ray scan; the words are the same either way.  The call enqueues one kernel on the
+ * context's stream and makes no host round trip once the scene is on the device, so it can be
+ * captured into a HIP graph like eray_cast_rays.  Errors (ERAY_E_INVALID_ARGUMENT): params NULL,
+ * unknown flags, reserved != 0, rays, targets or out NULL with count > 0.  count == 0 returns
+ * ERAY_OK with nothing launched.  Present in builds that define ERAY_HAS_REACH_LIGHT. */
+#define ERAY_HAS_REACH_LIGHT 1
+typedef struct eray_reach_params {      /*                                                40 B */
+    const eray_ray* rays;               /* offset 0:  device, count shadow rays                */
+    const float* targets;               /* offset 8:  device, count x 3: the light's position  */
+    uint64_t count;                     /* offset 16 */
+    uint32_t flags;                     /* offset 24: ERAY_RAYS_NORMALIZE | ERAY_RAYS_BRUTE_FORCE */
+    uint32_t reserved;                  /* offset 28: 0 */
+    uint32_t* out;                      /* offset 32: device, count words: 1 reaches, 0 blocked */
+} eray_reach_params;
+int eray_rays_reach_light(eray_ctx* ctx, const eray_reach_params* params);
 
 /* ------------------------------------------------------------------ multi-GPU ----------- *
  * One process (one context) per GPU; a frame is split into row tiles and gathered on rank 0

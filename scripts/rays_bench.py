@@ -2,6 +2,7 @@
 
     python scripts/rays_bench.py [--repeats 5] [--small-only] [--no-1m] [--out FILE.json]
     python scripts/rays_bench.py --accel-build both [--repeats 5] [--no-1m] [--out FILE.json]
+    python scripts/rays_bench.py --secondary [--repeats 5] [--out FILE.jsonl]
 
 Two cameras, main.rs's scene: C2 (1920x1080, cube.obj) and 3840x2160 over the 69,451-face
 stand-in mesh (bench.py's north-star scene).  The rays are the camera's own pixel-corner rays
@@ -29,6 +30,13 @@ one untimed round (build_ms: host wall time of the whole call, final synchronisa
 and the query workloads (2^22 incoherent rays / 69k, 2^20 / 1M, the 3840x2160 camera's rays / 69k)
 timed by device events through each builder's tree, alternating likewise, the records compared
 byte for byte between the trees.
+
+--secondary measures out_rgb's shadow and reflected rays instead: C2's cube scene (no hierarchy
+object), then the 69,451-face mesh with its true box, two point lights and a reflective material
+through the host-built hierarchy — 2^20 incoherent rays and the 3840x2160 camera's rays, bounces 0
+and 2 — and eray_rays_reach_light for 2^20 shadow rays with the hierarchy and with the tiles.  For a
+same-session comparison run it once per library (ERAY_LIB=<the parent commit's build>, then the
+product), alternating; --out appends.  A library that predates eray_rays_reach_light skips that leg.
 """
 from __future__ import annotations
 
@@ -292,6 +300,152 @@ def bench_accel_build(which: str, repeats: int, no_1m: bool) -> list:
     return lines
 
 
+def timed_forms(stream, forms: dict, repeats: int) -> dict:
+    """`repeats` device-event timings of each form, alternating, after one untimed round."""
+    times = {k: [] for k in forms}
+    for rep in range(repeats + 1):  # round 0: warm-up
+        for k, fn in forms.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            fn()
+            t1.record(stream)
+            t1.synchronize()
+            if rep:
+                times[k].append(t0.elapsed_time(t1))
+    return {k: summary(v) for k, v in times.items()}
+
+
+SECONDARY_LIGHTS = ((4.0, 3.0, 2.0), (-4.5, 3.5, 0.5))
+
+
+def bench_secondary_large(repeats: int) -> dict:
+    """out_rgb on the 69,451-face mesh with its true box, two point lights, one ambient light and a
+    1 x 1 reflection image of 0.5 (so that bounces = 2 casts reflected rays), through the host-built
+    hierarchy: 2^20 incoherent rays and the 3840x2160 camera's rays, bounces 0 and 2; the colours
+    are checked byte for byte against the context without a hierarchy on the incoherent rays.  Then
+    eray_rays_reach_light (where the library has it) for 2^20 shadow rays formed from those rays'
+    hits, with the hierarchy and with the tiles."""
+    stream = torch.cuda.Stream()
+    mesh = generated_mesh(**meshgen.STANDIN_70K)
+    lo, hi = mesh[0].reshape(-1, 3).min(0), mesh[0].reshape(-1, 3).max(0)
+    ctxs, bufs = [], []
+    try:
+        for _ in range(2):
+            c = capi.Context(0)
+            ctxs.append(c)
+            c.set_stream(stream.cuda_stream)
+            c.set_camera(capi.make_camera((0.0, 0.0, 5.0), (60.0, 60.0), 64, 1.0))
+            refl = c.to_device(np.full((1, 1), 0.5, np.float32))
+            bufs.append(refl)
+            c.add_object(*mesh, tuple(lo), tuple(hi), reflection=refl.image())
+            for p in SECONDARY_LIGHTS:
+                c.add_light(capi.make_light(p, "point"))
+            c.add_light(capi.make_light((0.0, 2.0, 0.0), "ambient", brightness=0.2))
+        ctx, actx = ctxs
+        info = actx.build_ray_accel()
+        out = {"workload": "secondary, 69451 faces, true box, 2 point lights", "repeats": repeats, "accel_info": info,
+               "lib": os.path.basename(capi.LIB_PATH)}
+        n = 1 << 20
+        inco_h = sphere_rays(n)
+        inco = ctx.to_device(inco_h)
+        cam_h = camera_rays((0.0, 0.0, 5.0), fov_for(3840, 2160), 3840, 2160)
+        cam = ctx.to_device(cam_h)
+        ncam = cam_h.shape[0]
+        rgb, hit = ctx.empty((ncam, 3), np.float32), ctx.empty((n,), capi.HIT_DTYPE)
+        bufs += [inco, cam, rgb, hit]
+        # the same colours with and without the hierarchy (the incoherent rays, bounces 2)
+        ctx.cast_rays_device(inco.ptr, n, out_hit=hit.ptr, out_rgb=rgb.ptr, bounces=2, flags=capi.RAYS_NORMALIZE)
+        ctx.synchronize()
+        want, hits = rgb.numpy()[:n].tobytes(), hit.numpy()
+        actx.cast_rays_device(inco.ptr, n, out_rgb=rgb.ptr, bounces=2, flags=capi.RAYS_NORMALIZE)
+        ctx.synchronize()
+        if rgb.numpy()[:n].tobytes() != want:
+            raise AssertionError("secondary: the hierarchy's out_rgb differs from the tiles'")
+        out["hit_rays_incoherent"] = int((hits["object"] >= 0).sum())
+        forms = {}
+        for b in (0, 2):
+            forms[f"rgb_incoherent_2^20_bounces{b}"] = lambda b=b: actx.cast_rays_device(
+                inco.ptr, n, out_rgb=rgb.ptr, bounces=b, flags=capi.RAYS_NORMALIZE)
+            forms[f"rgb_camera_3840x2160_bounces{b}"] = lambda b=b: actx.cast_rays_device(
+                cam.ptr, ncam, out_rgb=rgb.ptr, bounces=b)
+        if hasattr(capi.lib(), "eray_rays_reach_light"):
+            ok = hits["object"] >= 0
+            P, N = hits["position"][ok], hits["normal"][ok]
+            S = (P + N * np.float32(0.1)).astype(np.float32)
+            sh, tg = [], []
+            for L in SECONDARY_LIGHTS:
+                d = np.float32(L) - P
+                sq = np.float32(0.0) + d[:, 0] * d[:, 0]
+                sq = sq + d[:, 1] * d[:, 1]
+                sq = sq + d[:, 2] * d[:, 2]
+                sh.append(np.concatenate([S, d / np.sqrt(sq)[:, None]], axis=1))
+                tg.append(np.tile(np.float32(L), (P.shape[0], 1)))
+            sh, tg = np.concatenate(sh), np.concatenate(tg)
+            idx = np.resize(np.arange(sh.shape[0]), n)  # (repeated from the start when fewer than 2^20)
+            d_sh, d_tg = ctx.to_device(np.ascontiguousarray(sh[idx], np.float32)), ctx.to_device(np.ascontiguousarray(tg[idx], np.float32))
+            words = ctx.empty((n,), np.uint32)
+            bufs += [d_sh, d_tg, words]
+            ctx.rays_reach_light_device(d_sh.ptr, d_tg.ptr, n, words.ptr)
+            ctx.synchronize()
+            w = words.numpy()
+            actx.rays_reach_light_device(d_sh.ptr, d_tg.ptr, n, words.ptr)
+            ctx.synchronize()
+            if words.numpy().tobytes() != w.tobytes():
+                raise AssertionError("secondary: the hierarchy's reach words differ from the tiles'")
+            out["reach_blocked"] = int((w == 0).sum())
+            forms["reach_2^20_accel"] = lambda: actx.rays_reach_light_device(d_sh.ptr, d_tg.ptr, n, words.ptr)
+            forms["reach_2^20_tiled"] = lambda: ctx.rays_reach_light_device(d_sh.ptr, d_tg.ptr, n, words.ptr)
+        out.update(timed_forms(stream, forms, repeats))
+        return out
+    finally:
+        for a in bufs:
+            a.free()
+        for c in ctxs:
+            c.close()
+
+
+def bench_secondary_small(repeats: int) -> dict:
+    """C2's cube scene (main.rs's, 1920x1080), out_rgb of the camera's rays: no object gets a
+    hierarchy, so the context without one runs rays_kernel, which the secondary-ray change leaves
+    alone; after a default build the same rays go through rays_accel_kernel with every object
+    scanned."""
+    stream = torch.cuda.Stream()
+    width, height = 1920, 1080
+    fov = fov_for(width, height)
+    mesh = load_obj_file(os.path.join(ROOT, "objects", "cube.obj"))
+    ctx = capi.Context(0)
+    ctx.set_stream(stream.cuda_stream)
+    scene = MainScene(ctx, *mesh, width, height, texture=1024, fov=fov)
+    actx = capi.Context(0)
+    actx.set_stream(stream.cuda_stream)
+    ascene = MainScene(actx, *mesh, width, height, texture=1024, fov=fov)
+    info = actx.build_ray_accel()
+    n = width * height
+    rays = ctx.to_device(camera_rays((0.0, 0.0, 5.0), fov, width, height))
+    rgb = ctx.empty((n, 3), np.float32)
+    try:
+        forms = {"rgb_cube_1920x1080": lambda: ctx.cast_rays_device(rays.ptr, n, out_rgb=rgb.ptr),
+                 "rgb_cube_1920x1080_after_build": lambda: actx.cast_rays_device(rays.ptr, n, out_rgb=rgb.ptr)}
+        forms["rgb_cube_1920x1080"]()
+        ctx.synchronize()
+        want = rgb.numpy().tobytes()
+        forms["rgb_cube_1920x1080_after_build"]()
+        ctx.synchronize()
+        if rgb.numpy().tobytes() != want:
+            raise AssertionError("secondary: the cube's out_rgb differs after the build")
+        out = {"workload": "secondary, C2 cube scene", "repeats": repeats, "accel_info": info,
+               "lib": os.path.basename(capi.LIB_PATH)}
+        out.update(timed_forms(stream, forms, repeats))
+        return out
+    finally:
+        rays.free()
+        rgb.free()
+        ascene.close()
+        actx.close()
+        scene.close()
+        ctx.close()
+
+
 def generated_mesh(triangles: int, seed: int):
     v, n, t, F, _, _ = meshgen.displaced_sphere(triangles, seed)
     return (v[F].reshape(triangles, 9).astype(np.float32), n[F].reshape(triangles, 9).astype(np.float32),
@@ -305,8 +459,20 @@ def main() -> None:
     ap.add_argument("--no-1m", action="store_true", help="skip the 1M-face incoherent workload")
     ap.add_argument("--accel-build", choices=("host", "device", "both"), default="",
                     help="measure the hierarchy's builders and the queries through their trees instead")
+    ap.add_argument("--secondary", action="store_true",
+                    help="measure out_rgb's secondary rays through the hierarchy and the reach query instead")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.secondary:
+        lines = []
+        for fn in (bench_secondary_small, bench_secondary_large):
+            lines.append(fn(a.repeats))
+            print(json.dumps(lines[-1]), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:  # (appended: one file collects the libraries of an A/B)
+                for ln in lines:
+                    f.write(json.dumps(ln) + "\n")
+        return
     if a.accel_build:
         lines = bench_accel_build(a.accel_build, a.repeats, a.no_1m)
         if a.out:
