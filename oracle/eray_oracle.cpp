@@ -557,15 +557,11 @@ int oracle_render(const oracle_object* objects, uint32_t object_count, const ora
                             row0, rows, bounces, 0, 0, out_rgb, out_face, out_object, stats);
 }
 
-// Engine::render restricted to the camera pixels [x0, x0 + cols) x rows [row0, row0 + rows):
-// the same per-pixel loop body (engine.rs:52-78), output pixel (x, y) at (y - row0) * stride +
-// (x - x0).  The whole-frame entry points pass x0 = 0, cols = camera width, stride = image width.
-static int render_region(const oracle_object* objects, uint32_t object_count, const oracle_light* lights,
-                         uint32_t light_count, const oracle_camera* cam, uint32_t image_width,
-                         uint32_t image_height, uint32_t row0, uint32_t rows, uint32_t x0, uint32_t cols,
-                         uint32_t stride, uint32_t bounces, uint32_t anti_aliasing, uint64_t seed, float* out_rgb,
-                         int32_t* out_face, int32_t* out_object, oracle_stats* stats) {
-    Engine e;
+// The Engine of a scene description: objects in scene order with their faces, boxes and material
+// images, then the lights.  Shared by every entry point that traces rays.
+static int make_engine(const oracle_object* objects, uint32_t object_count, const oracle_light* lights,
+                       uint32_t light_count, const oracle_camera* cam, uint32_t bounces, Engine* out) {
+    Engine& e = *out;
     e.camera = to_camera(cam);
     e.bounces = bounces;
     e.stats = oracle_stats{0, 0, 0};
@@ -591,6 +587,20 @@ static int render_region(const oracle_object* objects, uint32_t object_count, co
         e.lights.push_back(Light{mk(l.position[0], l.position[1], l.position[2]), l.variant,
                                  Color{l.color[0], l.color[1], l.color[2]}, l.brightness});
     }
+    return ORACLE_OK;
+}
+
+// Engine::render restricted to the camera pixels [x0, x0 + cols) x rows [row0, row0 + rows):
+// the same per-pixel loop body (engine.rs:52-78), output pixel (x, y) at (y - row0) * stride +
+// (x - x0).  The whole-frame entry points pass x0 = 0, cols = camera width, stride = image width.
+static int render_region(const oracle_object* objects, uint32_t object_count, const oracle_light* lights,
+                         uint32_t light_count, const oracle_camera* cam, uint32_t image_width,
+                         uint32_t image_height, uint32_t row0, uint32_t rows, uint32_t x0, uint32_t cols,
+                         uint32_t stride, uint32_t bounces, uint32_t anti_aliasing, uint64_t seed, float* out_rgb,
+                         int32_t* out_face, int32_t* out_object, oracle_stats* stats) {
+    Engine e;
+    int st = make_engine(objects, object_count, lights, light_count, cam, bounces, &e);
+    if (st) return st;
     uint32_t width, height;
     camera_size(e.camera, &width, &height);
     if (row0 + rows > height) return ORACLE_E_ARG;
@@ -656,6 +666,82 @@ int oracle_render_span(const oracle_object* objects, uint32_t object_count, cons
     camera_size(to_camera(cam), &width, &height);
     return render_region(objects, object_count, lights, light_count, cam, width, height, row0, rows, x0, cols, cols,
                          0, 0, 0, out_rgb, out_face, nullptr, stats);
+}
+
+// ------------------------------------------------------------ caller-supplied rays ----------
+namespace {
+// One ray of a count x 6 array: Ray::new (raycasting.rs:16-21) with the flag, else the stored dir.
+Ray ray_at(const float* rays, uint64_t i, int normalize) {
+    const float* r = rays + 6 * i;
+    V3 start = mk(r[0], r[1], r[2]), dir = mk(r[3], r[4], r[5]);
+    return normalize ? ray_new(start, dir) : Ray{start, dir};
+}
+// The record of Object k's hit.  RaycastHit holds neither the barycentrics nor the uv that
+// Object::intersects folds (object.rs:70-72), so the hit face's Triangle::intersects is called
+// once more for them: the same inputs give the same bits.
+void fill_hit(const Object& obj, const Ray& ray, const Hit& h, int32_t k, oracle_ray_hit* out) {
+    const Triangle& f = obj.faces[h.face_index];
+    V3 pos, nrm, bary;
+    triangle_intersects(f, ray, &pos, &nrm, &bary);
+    V2 uv = add2(add2(mul2(f.a.uv, bary.v[2]), mul2(f.b.uv, bary.v[0])), mul2(f.c.uv, bary.v[1]));
+    out->object = k;
+    out->face = (int32_t)h.face_index;
+    std::memcpy(out->position, h.position.v, sizeof out->position);
+    std::memcpy(out->normal, h.normal.v, sizeof out->normal);
+    std::memcpy(out->uv, uv.v, sizeof out->uv);
+    out->u = bary.v[0];
+    out->v = bary.v[1];
+}
+}  // namespace
+
+int oracle_cast_rays(const oracle_object* objects, uint32_t object_count, const oracle_light* lights,
+                     uint32_t light_count, const oracle_camera* cam, uint32_t bounces, const float* rays,
+                     uint64_t count, int normalize, int32_t object, oracle_ray_hit* out_hit, float* out_rgb) {
+    if (object < -1 || (object >= 0 && ((uint32_t)object >= object_count || out_rgb))) return ORACLE_E_ARG;
+    if (count && !rays) return ORACLE_E_ARG;
+    Engine e;
+    int st = make_engine(objects, object_count, lights, light_count, cam, bounces, &e);
+    if (st) return st;
+    std::vector<Color> lighting;
+    uint64_t tests = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        Ray ray = ray_at(rays, i, normalize);
+        int32_t winner = object;
+        if (object < 0) {  // Engine::cast_ray's own selection (engine.rs:116-126) and its list
+            int32_t face = -1;
+            e.cast_ray(ray, 0, lighting, &face, &winner);
+            if (out_rgb) {
+                Color sum = color_sum(lighting);
+                out_rgb[3 * i + 0] = sum.r;
+                out_rgb[3 * i + 1] = sum.g;
+                out_rgb[3 * i + 2] = sum.b;
+            }
+        }
+        if (!out_hit) continue;
+        oracle_ray_hit rec;
+        std::memset(&rec, 0, sizeof rec);
+        rec.object = -1;
+        Hit h;
+        if (winner >= 0 && object_intersects(e.objects[winner], ray, &h, &tests))
+            fill_hit(e.objects[winner], ray, h, winner, &rec);
+        out_hit[i] = rec;
+    }
+    return ORACLE_OK;
+}
+
+int oracle_rays_reach_light(const oracle_object* objects, uint32_t object_count, const float* rays,
+                            const float* targets, uint64_t count, int normalize, uint32_t* out) {
+    if (count && (!rays || !targets || !out)) return ORACLE_E_ARG;
+    Engine e;
+    oracle_camera cam = {{0.0f, 0.0f, 0.0f}, 1.0f, 1.0f, 1u, 1.0f};  // (reaches_light reads no camera)
+    int st = make_engine(objects, object_count, nullptr, 0, &cam, 0, &e);
+    if (st) return st;
+    for (uint64_t i = 0; i < count; ++i) {
+        const float* t = targets + 3 * i;
+        Light light{mk(t[0], t[1], t[2]), 0, Color{0.0f, 0.0f, 0.0f}, 0.0f};
+        out[i] = e.reaches_light(ray_at(rays, i, normalize), light) ? 1u : 0u;
+    }
+    return ORACLE_OK;
 }
 
 int oracle_ppm_bytes(const float* rgb, uint32_t width, uint32_t height, uint8_t* out) {

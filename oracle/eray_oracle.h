@@ -132,6 +132,31 @@ int oracle_render_span(const oracle_object* objects, uint32_t object_count,
 void oracle_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 float oracle_jitter(uint32_t word);
 
+/* --- caller-supplied rays: Object::intersects, Engine::cast_ray, Engine::reaches_light ---- *
+ * A record has the layout and meaning of the product's eray_ray_hit (restated, not shared):
+ * RaycastHit (raycasting.rs:43-54) plus the uv and barycentrics of the hit face.              */
+typedef struct {                 /* 48 B */
+    int32_t object;              /* scene index, -1: no hit (the rest is then 0) */
+    int32_t face;                /* RaycastHit::face_index (object.rs:63-78) */
+    float position[3];           /* start + dir * t (primitives.rs:66) */
+    float normal[3];             /* normalize(na*u + nb*v + nc*t) (primitives.rs:67) */
+    float uv[2];                 /* a.uv*w + b.uv*u + c.uv*v (object.rs:70-72, in that order) */
+    float u, v;                  /* barycentric[0], [1] (primitives.rs:60-61, 69) */
+} oracle_ray_hit;
+/* rays: count x 6 floats (start xyz, dir xyz); with `normalize` dir goes through Ray::new
+ * (raycasting.rs:16-21), else it is the Ray's stored dir.  object == -1: the record of the object
+ * that wins Engine::cast_ray's selection (engine.rs:116-126) and, in out_rgb (optional, count x 3),
+ * color_sum(cast_ray(ray, 0)) with Engine::bounces = bounces.  object == k: Object k's
+ * Object::intersects alone (out_rgb must be NULL).  out_hit is optional too. */
+int oracle_cast_rays(const oracle_object* objects, uint32_t object_count,
+                     const oracle_light* lights, uint32_t light_count, const oracle_camera* cam,
+                     uint32_t bounces, const float* rays, uint64_t count, int normalize,
+                     int32_t object, oracle_ray_hit* out_hit, float* out_rgb);
+/* Engine::reaches_light (engine.rs:218-228) per ray, the light's position being targets[i]
+ * (count x 3 floats): out[i] = 1 the ray reaches it, 0 an object blocks it. */
+int oracle_rays_reach_light(const oracle_object* objects, uint32_t object_count, const float* rays,
+                            const float* targets, uint64_t count, int normalize, uint32_t* out);
+
 /* Image<Color>::save_as_ppm body bytes (image.rs:48-74): rows bottom-up, sat-u8 bytes. */
 int oracle_ppm_bytes(const float* rgb, uint32_t width, uint32_t height, uint8_t* out);
 /* "P6 {w} {h} 255\n" (image.rs:56); returns header length. */

@@ -258,6 +258,53 @@ def render_span(scene: Scene, cam: Camera, row0: int, rows: int, x0: int, cols: 
     return out, faces, dict(primary_tests=st.primary_tests, shadow_tests=st.shadow_tests, hit_pixels=st.hit_pixels)
 
 
+# ---------------------------------------------------------------- caller-supplied rays ---
+# oracle_ray_hit (eray_oracle.h): stated here on its own, not taken from the product's binding.
+HIT_DTYPE = np.dtype([("object", np.int32), ("face", np.int32), ("position", np.float32, 3),
+                      ("normal", np.float32, 3), ("uv", np.float32, 2), ("u", np.float32), ("v", np.float32)])
+assert HIT_DTYPE.itemsize == 48
+
+
+def _rays(rays):
+    return np.ascontiguousarray(np.asarray(rays, np.float32).reshape(-1, 6))
+
+
+def cast_rays(scene: Scene, cam: Camera, rays, bounces=0, normalize=False, object=-1, want_rgb=False):
+    """Object::intersects / Engine::cast_ray for the (n, 6) rays (start xyz, dir xyz).  Returns the
+    HIT_DTYPE records (object == -1: a miss, the rest 0): of cast_ray's winner for object = -1, of
+    Object k alone for object = k; with want_rgb also the (n, 3) color_sum(cast_ray(ray, 0))."""
+    r = _rays(rays)
+    n = r.shape[0]
+    hits = np.zeros(n, HIT_DTYPE)
+    rgb = np.zeros((n, 3), np.float32) if want_rgb else None
+    objs = (Object * max(1, len(scene.objects)))(*scene.objects)
+    lights = (Light * max(1, len(scene.lights)))(*scene.lights)
+    rc = lib().oracle_cast_rays(objs, len(scene.objects), lights, len(scene.lights), C.byref(cam),
+                                C.c_uint32(bounces), _fp(r), C.c_uint64(n), int(bool(normalize)),
+                                C.c_int32(object), hits.ctypes.data_as(C.c_void_p),
+                                _fp(rgb) if want_rgb else None)
+    if rc:
+        raise ValueError(f"oracle_cast_rays status {rc}")
+    return (hits, rgb) if want_rgb else hits
+
+
+def reach_light(scene: Scene, rays, targets, normalize=False) -> np.ndarray:
+    """Engine::reaches_light per ray with targets[i] (n, 3) as the light's position: n uint32 words,
+    1 the ray reaches it, 0 an object blocks it."""
+    r = _rays(rays)
+    t = np.ascontiguousarray(np.asarray(targets, np.float32).reshape(-1, 3))
+    n = r.shape[0]
+    if t.shape[0] != n:
+        raise ValueError("rays and targets disagree on the count")
+    out = np.zeros(n, np.uint32)
+    objs = (Object * max(1, len(scene.objects)))(*scene.objects)
+    rc = lib().oracle_rays_reach_light(objs, len(scene.objects), _fp(r), _fp(t), C.c_uint64(n),
+                                       int(bool(normalize)), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc:
+        raise ValueError(f"oracle_rays_reach_light status {rc}")
+    return out
+
+
 def philox4x32_10(ctr, key):
     """Philox4x32-10 block (the anti-aliasing jitter stream, oracle_render_aa)."""
     c, k, o = (C.c_uint32 * 4)(*ctr), (C.c_uint32 * 2)(*key), (C.c_uint32 * 4)()

@@ -13,6 +13,8 @@
 //   rebuild    1 when a second build gave the same bytes                          (c)
 //   deep       1 when the builder refused a tree deeper than a too-small stack    (d)
 //   tests_per_ray, unculled, fallback_in_range                                    (e)
+// Then sphere2000 and the sliver mesh again, moved and scaled with their rays (moved_suite): the
+// same figures (a), (b) and the fallback counts, min(rays, 20000) rays each.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -329,6 +331,53 @@ bool suite(const char* name, const std::vector<float>& pos, size_t nrays, size_t
            b.depth <= bound;
 }
 
+// The mesh moved to x * s + t and the sphere distribution's rays moved with it (start * s + t,
+// direction * s * k), both in double before the rounding to f32: long directions (step 5 of the
+// margin proof, where rounding alone can lift det over 1e-6) and meshes far from the origin (the
+// |a|1 term of beta).  Every such ray is finite with |o|1 and |d|inf far inside accel_covered's
+// range, so in_range is true by construction: none may fall back.
+// Every other ray has suite()'s long direction (kLong times the unit distribution's) under the
+// same s * k.  With s = 1e-2 and k = 1 a face's n shrinks by 1e-4 and a unit-distribution direction
+// by 1e-2: det = -d . n is at most 6e-8 on sphere2000 and Triangle::intersects' det >= 1e-6 fails
+// every face, so only the long rays give that setting pairs to check.
+constexpr double kLong = 1e3 / 4.5;
+bool moved_suite(const char* name, const std::vector<float>& unit, double s, double t, double k, size_t nrays) {
+    const uint32_t T = (uint32_t)(unit.size() / 9);
+    std::vector<float> pos(unit.size());
+    for (size_t i = 0; i < unit.size(); ++i) pos[i] = (float)((double)unit[i] * s + t);
+    std::vector<Hot> hot(T);
+    for (uint32_t f = 0; f < T; ++f) hot[f] = make_hot(&pos[9 * (size_t)f]);
+    Built b;
+    const char* why = "";
+    if (!build_object(hot.data(), T, 0, 0, kStackDepth, &b, &why)) {
+        std::printf("%s: build refused: %s\n", name, why);
+        return false;
+    }
+    std::vector<Ray> rays;
+    for (size_t i = 0; i < nrays; ++i) {
+        double v[3] = {gauss(), gauss(), gauss()};
+        const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        double o[3], d[3];
+        for (int c = 0; c < 3; ++c) {
+            const double start = 3.0 * v[c] / l;
+            o[c] = start * s + t;
+            d[c] = (uni(-1, 1) - start) * (i % 2 ? kLong : 1.0) * s * k;
+        }
+        Ray r = mk(o, d);
+        r.in_range = true;
+        rays.push_back(r);
+    }
+    Result r;
+    run(hot, b, rays, rays.size(), r);
+    std::printf(
+        "suite=%s faces=%u nodes=%zu depth=%u unculled=%u rays=%zu mismatch=%llu violation=%llu pairs=%llu "
+        "sphere_hits=%llu fallback=%llu fallback_in_range=%llu stack_high=%u\n",
+        name, T, b.nodes.size(), b.depth, b.unculled, rays.size(), (unsigned long long)r.mismatch,
+        (unsigned long long)r.violation, (unsigned long long)r.pairs, (unsigned long long)r.hits,
+        (unsigned long long)r.fallback, (unsigned long long)r.fallback_in_range, r.stack_high);
+    return r.mismatch + r.violation + r.fallback == 0;
+}
+
 bool load(const char* path, std::vector<float>& pos) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return false;
@@ -395,6 +444,14 @@ int main(int argc, char** argv) {
     ok &= suite("soup300", soup(300, 1.0, 0.2), nrays, nrays);
     ok &= suite("cube", cube(), nrays, nrays);
     ok &= suite("slivers", slivers(600), nrays, nrays);
+    // (s, t, k) of moved_suite, in this order in the suites' names: _m0 .. _m4
+    static const double moves[5][3] = {{1, 0, 1e6}, {1, 1000, 1}, {1, 1000, 1e5}, {1e-2, 5, 1e4}, {1e-2, 0, 1}};
+    const std::vector<float> sliver_mesh = slivers(600);
+    for (int m = 0; m < 5; ++m) {
+        const size_t n = std::min<size_t>(nrays, 20000);
+        ok &= moved_suite(("sphere2000_m" + std::to_string(m)).c_str(), s2k, moves[m][0], moves[m][1], moves[m][2], n);
+        ok &= moved_suite(("slivers_m" + std::to_string(m)).c_str(), sliver_mesh, moves[m][0], moves[m][1], moves[m][2], n);
+    }
     std::printf(ok ? "OK\n" : "FAILED\n");
     return ok ? 0 : 1;
 }

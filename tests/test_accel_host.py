@@ -65,7 +65,7 @@ def test_walk_equals_the_scan_and_nodes_hold_their_faces(walk):
     has its leaf and all its ancestors pass the node test, unless the face is unculled or the ray a
     fallback ray; the slots are a permutation of the faces, byte copies of their records."""
     r, fig = walk
-    assert set(fig) == set(SUITES), r.stdout + r.stderr
+    assert set(fig) == set(SUITES) | set(MOVED_SUITES), r.stdout + r.stderr
     for name in SUITES:
         f = fig[name]
         assert f["rays"] >= 100000, name
@@ -97,6 +97,27 @@ def test_honesty_caps(walk):
         assert fig[name]["fallback_in_range"] == 0, name
         assert fig[name]["fallback"] >= 48, name  # the non-finite rays do fall back
     assert fig["cube"]["unculled"] == 12 and fig["cube"]["nodes"] == 0
+
+
+MOVES = ((1, 0, 1e6), (1, 1000, 1), (1, 1000, 1e5), (1e-2, 5, 1e4), (1e-2, 0, 1))  # (s, t, k), the program's order
+MOVED_SUITES = tuple(f"{mesh}_m{m}" for m in range(len(MOVES)) for mesh in ("sphere2000", "slivers"))
+
+
+@pytest.mark.parametrize("name", MOVED_SUITES)
+def test_moved_meshes_and_scaled_directions(walk, name):
+    """sphere2000 and the sliver mesh moved to x * s + t with the rays' directions scaled by s * k:
+    directions up to 5e6 long (step 5 of accel_build.hpp's margin proof) and meshes 1000 units from
+    the origin (beta's |a|1 term).  20,000 rays each, all inside accel_covered's range by
+    construction: none falls back, the walk equals the scan, no passing face's leaf or ancestor
+    fails the node test, and faces remain under the tree (an empty tree would test nothing)."""
+    r, fig = walk
+    assert name in fig, r.stdout + r.stderr
+    f = fig[name]
+    assert f["rays"] == 20000, f
+    assert f["mismatch"] == 0 and f["violation"] == 0, f
+    assert f["fallback"] == 0 and f["fallback_in_range"] == 0, f
+    assert f["pairs"] >= 3000, f
+    assert f["unculled"] < f["faces"] and f["nodes"] > 0, f
 
 
 def test_walk_program_under_asan_ubsan(sphere_files, tmp_path):

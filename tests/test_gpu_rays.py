@@ -2,17 +2,15 @@
 and Engine::cast_ray (engine.rs:112-216) for caller-supplied rays.
 
 Bar: every comparison is bit for bit (integer equality, helpers.assert_bit_equal).  References:
-a hand-derived record, the oracle's render for camera rays, and for arbitrary rays a per-face
-reference built here from the oracle's Triangle::intersects in face order, with
-BoundingBox::intersects (object.rs:327-379), the uv fold (object.rs:70-72) and the closest-object
-len_sq fold (engine.rs:120-126) restated in np.float32.
+a hand-derived record, the oracle's render for camera rays, and for arbitrary rays the oracle's
+Object::intersects per object (oracle.cast_rays(object=k)), with the closest-object len_sq fold
+(engine.rs:120-126) restated in np.float32 and the oracle's own selection beside it.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from eray_amd import capi
+from tests import ray_refs as R
 from tests.helpers import assert_bit_equal, random_mesh
 
 pytestmark = pytest.mark.gpu
@@ -20,86 +18,20 @@ pytestmark = pytest.mark.gpu
 MISS_RGB = np.float32([0.1, 0.1, 0.2])  # engine.rs:211-213
 
 
-# ------------------------------------------------------------------ the per-face reference ---
-def normalize_f32(d):
-    """Ray::new's dir.normalize() (raycasting.rs:16-21, vector.rs:150-158): the len_sq fold from
-    0, sqrt, one division per component — all in f32."""
-    d = np.asarray(d, np.float32)
-    sq = np.float32(0.0) + d[:, 0] * d[:, 0]
-    sq = sq + d[:, 1] * d[:, 1]
-    sq = sq + d[:, 2] * d[:, 2]
-    return (d / np.sqrt(sq)[:, None]).astype(np.float32)
+# ------------------------------------------------------------------ the reference -----------
+def object_records(oracle, mesh, lo, hi, start, raw_dir):
+    """Object::intersects (object.rs:58-81) of one object with the box (lo, hi), per ray: the
+    oracle's own loop (oracle.cast_rays(object=0)), raw_dir going through Ray::new as a ray passed
+    with ERAY_RAYS_NORMALIZE does on the device.  (tests/test_oracle_rays.py holds it to the
+    per-face loop over Triangle::intersects that this file used to run itself.)"""
+    s = oracle.Scene()
+    s.add_object(*mesh, tuple(lo), tuple(hi))
+    return oracle.cast_rays(s, oracle.camera(), R.rays_array(start, raw_dir), normalize=True, object=0)
 
 
-def bbox_intersects(lo, hi, start, d):
-    """BoundingBox::intersects (object.rs:327-379) for rays (start, stored dir d), in f32; a zero
-    direction component gives infinite (and, where the slab's numerator is 0 too, NaN) bounds,
-    which the comparisons treat as the reference does (a comparison with NaN is false)."""
-    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
-    start, d = np.asarray(start, np.float32), np.asarray(d, np.float32)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        inv = np.float32(1.0) / d                                 # div_under(1.)     object.rs:330
-        neg = inv < 0                                             # signs            object.rs:331-337
-        tmin = (np.where(neg, hi, lo) - start) * inv              # bounds[sign]     object.rs:340,343,358
-        tmax = (np.where(neg, lo, hi) - start) * inv              # bounds[1 - sign] object.rs:341,344,359
-        txmin, txmax = tmin[:, 0].copy(), tmax[:, 0].copy()
-        out = ~((txmin > tmax[:, 1]) | (tmin[:, 1] > txmax))      # object.rs:346-348
-        txmin = np.where(tmin[:, 1] > txmin, tmin[:, 1], txmin)   # object.rs:350-352
-        txmax = np.where(tmax[:, 1] < txmax, tmax[:, 1], txmax)   # object.rs:354-356
-        txmin = np.where(tmin[:, 2] > txmin, tmin[:, 2], txmin)   # object.rs:361-363
-        txmax = np.where(tmax[:, 2] < txmax, tmax[:, 2], txmax)   # object.rs:365-367
-        out &= ~((txmin < 0) & (txmax < 0))                       # object.rs:369-376
-    return out
-
-
-def first_hits(oracle, mesh, start, raw_dir):
-    """Per ray the first face in index order whose Triangle::intersects passes (object.rs:63-78),
-    ignoring the box: records with object 0 (-1: none).  raw_dir goes through Ray::new inside the
-    oracle, as a ray passed with ERAY_RAYS_NORMALIZE does on the device."""
-    pos, nrm, uv = mesh
-    L = oracle.lib()
-    faces = [((C.c_float * 9)(*pos[f]), (C.c_float * 9)(*nrm[f])) for f in range(pos.shape[0])]
-    p, n, b = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
-    out = np.zeros(start.shape[0], capi.HIT_DTYPE)
-    out["object"] = -1
-    for i in range(start.shape[0]):
-        s, d = (C.c_float * 3)(*start[i]), (C.c_float * 3)(*raw_dir[i])
-        for f, (fp, fn) in enumerate(faces):
-            if L.oracle_triangle_intersects(fp, fn, s, d, p, n, b):
-                bu, bv, bw = np.float32(b[0]), np.float32(b[1]), np.float32(b[2])
-                a_uv, b_uv, c_uv = uv[f, 0:2], uv[f, 2:4], uv[f, 4:6]
-                out[i] = (0, f, tuple(p), tuple(n), tuple((a_uv * bw + b_uv * bu) + c_uv * bv), bu, bv)  # object.rs:70-72
-                break
-    return out
-
-
-def with_box(first, lo, hi, start, d):
-    """Object::intersects: the box first (object.rs:59), then the face search's result."""
-    out = first.copy()
-    miss = ~bbox_intersects(lo, hi, start, d)
-    out[miss] = np.zeros((), capi.HIT_DTYPE)
-    out["object"][miss] = -1
-    return out, miss
-
-
-def closest_by_centre(per_object, centre):
-    """cast_ray's selection (engine.rs:116-126): in scene order an object replaces the current one
-    only when |position - camera.centre|² (the fold from 0, f32) is strictly smaller."""
-    centre = np.float32(centre)
-    n = per_object[0].shape[0]
-    out = np.zeros(n, capi.HIT_DTYPE)
-    out["object"] = -1
-    best = np.zeros(n, np.float32)
-    for k, h in enumerate(per_object):
-        e = h["position"] - centre
-        dsq = np.float32(0.0) + e[:, 0] * e[:, 0]
-        dsq = dsq + e[:, 1] * e[:, 1]
-        dsq = dsq + e[:, 2] * e[:, 2]
-        take = (h["object"] >= 0) & ((out["object"] < 0) | (dsq < best))
-        out[take] = h[take]
-        out["object"][take] = k
-        best[take] = dsq[take]
-    return out
+def box_rejects(lo, hi, start, d):
+    """The rays BoundingBox::intersects (object.rs:327-379) turns away, restated in f32 numpy."""
+    return ~R.bbox_intersects(lo, hi, start, d)
 
 
 def assert_hits_equal(got, want, what):
@@ -130,8 +62,8 @@ def sphere_rays(rng, n):
 
 
 @pytest.fixture(scope="module")
-def arbitrary(oracle):
-    """Test 3's mesh, rays and box-free first hits (the slow part of the reference, computed once)."""
+def arbitrary():
+    """Test 3's mesh and rays."""
     rng = np.random.default_rng(7)
     mesh = soup(rng, 300)
     start, raw = sphere_rays(rng, 512)
@@ -142,8 +74,7 @@ def arbitrary(oracle):
     extra_d = np.float32([[0.0, 0.0, -1.0], [0.0, 0.0, -2.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0], [0.0, -1.0, 0.0],
                           [0.0, -0.5, -1.0], [0.0, 0.0, 1.0], [0.0, 1.0, 0.0]])
     start, raw = np.concatenate([start, extra_s]), np.concatenate([raw, extra_d])
-    return {"mesh": mesh, "start": start, "raw": raw, "dir": normalize_f32(raw),
-            "first": first_hits(oracle, mesh, start, raw)}
+    return {"mesh": mesh, "start": start, "raw": raw, "dir": R.normalize_f32(raw)}
 
 
 def rays_array(start, d):
@@ -234,15 +165,17 @@ def test_camera_rays_equal_the_render(gpu, oracle, cube):
 
 
 # ------------------------------------------------------------------ 3. arbitrary rays --------
-def test_arbitrary_rays_equal_the_per_face_reference(gpu, arbitrary):
+def test_arbitrary_rays_equal_the_per_face_reference(gpu, oracle, arbitrary):
     """300 small faces, 512 sphere rays passed with ERAY_RAYS_NORMALIZE (plus axis-parallel ones):
     a general box, a tight box that rejects many rays, and the loaded meshes' (0,0,0) point box;
     the tiled search and ERAY_RAYS_BRUTE_FORCE both equal the reference."""
     A = arbitrary
-    first, start, d = A["first"], A["start"], A["dir"]
+    start, d = A["start"], A["dir"]
     refs = {}
     for name, h in (("wide", 1.2), ("tight", 0.5), ("point", 0.0)):
-        refs[name] = with_box(first, (-h,) * 3, (h,) * 3, start, d)
+        refs[name] = (object_records(oracle, A["mesh"], (-h,) * 3, (h,) * 3, start, A["raw"]),
+                      box_rejects((-h,) * 3, (h,) * 3, start, d))
+        assert not (refs[name][0]["object"][refs[name][1]] >= 0).any()  # the two statements of the box agree
     # conditions of the test, on its own reference, before any GPU call
     wide, wide_rej = refs["wide"]
     tight, tight_rej = refs["tight"]
@@ -273,14 +206,18 @@ def test_closest_object_is_chosen_by_the_cameras_centre(gpu, oracle, arbitrary):
     rng = np.random.default_rng(11)
     centre = (0.0, 5.0, 0.0)
     meshes = [random_mesh(rng, 40, center=(0.0, 0.0, 0.0)), random_mesh(rng, 40, center=(0.3, 0.0, 0.2))]
-    start, raw, d = arbitrary["start"][:256], arbitrary["raw"][:256], arbitrary["dir"][:256]
+    start, raw = arbitrary["start"], arbitrary["raw"]  # (every ray: the oracle's loop is fast)
     per, boxes = [], []
+    both_objects = oracle.Scene()
     for m in meshes:
         lo, hi = m[0].reshape(-1, 3).min(0), m[0].reshape(-1, 3).max(0)
         boxes.append((lo, hi))
-        per.append(with_box(first_hits(oracle, m, start, raw), lo, hi, start, d)[0])
-    want = closest_by_centre(per, centre)
-    by_start = np.full(256, -1)
+        per.append(object_records(oracle, m, lo, hi, start, raw))
+        both_objects.add_object(*m, tuple(lo), tuple(hi))
+    want = R.closest_by_centre(per, centre)
+    chosen = oracle.cast_rays(both_objects, oracle.camera(centre, (60.0, 60.0), 64, 1.0), R.rays_array(start, raw), normalize=True)
+    assert_hits_equal(chosen, want, "the oracle's selection and the numpy one")
+    by_start = np.full(start.shape[0], -1)
     both = (per[0]["object"] >= 0) & (per[1]["object"] >= 0)
     t0 = np.linalg.norm(per[0]["position"].astype(np.float64) - start, axis=1)
     t1 = np.linalg.norm(per[1]["position"].astype(np.float64) - start, axis=1)
@@ -316,16 +253,14 @@ def tile_meshes(oracle):
         pos[:, 2::3] *= np.float32(0.5)  # the soup between z = -0.6 and 0.6
         pos[T - 1] = np.float32([-2, -2, -1, 2, -2, -1, 0, 3, -1])  # a big face behind it, facing +z
         mesh = (pos, nrm, uv)
-        out[T] = (mesh, first_hits(oracle, mesh, start, raw))
+        out[T] = (mesh, object_records(oracle, mesh, (-2, -2, -1), (2, 3, 0.7), start, raw))
     return start, raw, out
 
 
 @pytest.mark.parametrize("T", [257, 513])
 def test_tile_boundaries_and_counts(gpu, tile_meshes, T):
     start, raw, meshes = tile_meshes
-    mesh, first = meshes[T]
-    d = normalize_f32(raw)
-    want, rej = with_box(first, (-2, -2, -1), (2, 3, 0.7), start, d)
+    mesh, want = meshes[T]
     assert (want["face"][want["object"] >= 0] == T - 1).sum() >= 100  # the face past the tile boundary
     assert (want["face"][want["object"] >= 0] < T - 1).sum() >= 100
     one_object_scene(gpu, mesh, (-2, -2, -1), (2, 3, 0.7))

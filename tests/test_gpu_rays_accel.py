@@ -5,93 +5,15 @@ with the same u, v, t bits.
 
 Bar: byte equality of whole record arrays (and of out_rgb) between the hierarchy, the LDS tiles
 (before the build, or after a drop) and ERAY_RAYS_BRUTE_FORCE; for the mixed scene also the
-per-face reference built from the oracle's Triangle::intersects (the helpers of
-tests/test_gpu_rays.py, copied)."""
-import ctypes as C
-
+oracle's records (oracle.cast_rays: Object::intersects per object and cast_ray's selection)."""
 import numpy as np
 import pytest
 
 from eray_amd import capi, meshgen
+from tests import ray_refs as R
 from tests.helpers import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
-
-
-# ------------------------------------------------------------------ the per-face reference ---
-def normalize_f32(d):
-    """Ray::new's dir.normalize() (raycasting.rs:16-21, vector.rs:150-158) in f32."""
-    d = np.asarray(d, np.float32)
-    sq = np.float32(0.0) + d[:, 0] * d[:, 0]
-    sq = sq + d[:, 1] * d[:, 1]
-    sq = sq + d[:, 2] * d[:, 2]
-    return (d / np.sqrt(sq)[:, None]).astype(np.float32)
-
-
-def bbox_intersects(lo, hi, start, d):
-    """BoundingBox::intersects (object.rs:327-379) for rays (start, stored dir d), in f32."""
-    lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
-    start, d = np.asarray(start, np.float32), np.asarray(d, np.float32)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        inv = np.float32(1.0) / d
-        neg = inv < 0
-        tmin = (np.where(neg, hi, lo) - start) * inv
-        tmax = (np.where(neg, lo, hi) - start) * inv
-        txmin, txmax = tmin[:, 0].copy(), tmax[:, 0].copy()
-        out = ~((txmin > tmax[:, 1]) | (tmin[:, 1] > txmax))
-        txmin = np.where(tmin[:, 1] > txmin, tmin[:, 1], txmin)
-        txmax = np.where(tmax[:, 1] < txmax, tmax[:, 1], txmax)
-        txmin = np.where(tmin[:, 2] > txmin, tmin[:, 2], txmin)
-        txmax = np.where(tmax[:, 2] < txmax, tmax[:, 2], txmax)
-        out &= ~((txmin < 0) & (txmax < 0))
-    return out
-
-
-def first_hits(oracle, mesh, start, raw_dir):
-    """Per ray the first face in index order whose Triangle::intersects passes (object.rs:63-78),
-    ignoring the box; raw_dir goes through Ray::new inside the oracle."""
-    pos, nrm, uv = mesh
-    L = oracle.lib()
-    faces = [((C.c_float * 9)(*pos[f]), (C.c_float * 9)(*nrm[f])) for f in range(pos.shape[0])]
-    p, n, b = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
-    out = np.zeros(start.shape[0], capi.HIT_DTYPE)
-    out["object"] = -1
-    for i in range(start.shape[0]):
-        s, d = (C.c_float * 3)(*start[i]), (C.c_float * 3)(*raw_dir[i])
-        for f, (fp, fn) in enumerate(faces):
-            if L.oracle_triangle_intersects(fp, fn, s, d, p, n, b):
-                bu, bv, bw = np.float32(b[0]), np.float32(b[1]), np.float32(b[2])
-                a_uv, b_uv, c_uv = uv[f, 0:2], uv[f, 2:4], uv[f, 4:6]
-                out[i] = (0, f, tuple(p), tuple(n), tuple((a_uv * bw + b_uv * bu) + c_uv * bv), bu, bv)
-                break
-    return out
-
-
-def with_box(first, lo, hi, start, d):
-    out = first.copy()
-    miss = ~bbox_intersects(lo, hi, start, d)
-    out[miss] = np.zeros((), capi.HIT_DTYPE)
-    out["object"][miss] = -1
-    return out
-
-
-def closest_by_centre(per_object, centre):
-    """cast_ray's selection (engine.rs:116-126) by |position - camera.centre|^2, strictly smaller."""
-    centre = np.float32(centre)
-    n = per_object[0].shape[0]
-    out = np.zeros(n, capi.HIT_DTYPE)
-    out["object"] = -1
-    best = np.zeros(n, np.float32)
-    for k, h in enumerate(per_object):
-        e = h["position"] - centre
-        dsq = np.float32(0.0) + e[:, 0] * e[:, 0]
-        dsq = dsq + e[:, 1] * e[:, 1]
-        dsq = dsq + e[:, 2] * e[:, 2]
-        take = (h["object"] >= 0) & ((out["object"] < 0) | (dsq < best))
-        out[take] = h[take]
-        out["object"][take] = k
-        best[take] = dsq[take]
-    return out
 
 
 def assert_hits_equal(got, want, what):
@@ -305,7 +227,8 @@ def test_smallest_index_wins(gpu, sphere3000):
 # ------------------------------------------------------------------ 3. mixed scene -----------
 def test_mixed_scene_selects_by_the_cameras_centre(gpu, oracle, cube, sphere3000):
     """The cube (below min_faces: LDS tiles), the sphere and a shifted copy (hierarchies), object =
-    -1: records equal the pre-build ones, and on 512 rays the per-face oracle reference."""
+    -1: records equal the pre-build ones, and on every ray the oracle's (each object alone, the
+    selection of engine.rs:116-126 restated in numpy over those, and the oracle's own selection)."""
     A = sphere3000
     centre = (0.5, 4.0, 1.0)
     shift = np.float32([0.6, 0.1, -0.2])
@@ -318,12 +241,16 @@ def test_mixed_scene_selects_by_the_cameras_centre(gpu, oracle, cube, sphere3000
                              expect={"objects": 2, "faces": 6000, "unculled_faces": 0})
     for k in range(3):
         assert (hits["object"] == k).sum() >= 50, k
-    n = 512
-    start, raw = A["start"][:n], A["raw"][:n]
-    d = normalize_f32(raw)
-    per = [with_box(first_hits(oracle, m, start, raw), lo, hi, start, d) for m, (lo, hi) in objects]
-    want = closest_by_centre(per, centre)
-    assert_hits_equal(gpu.cast_rays(rays[:n], normalize=True), want, "mixed scene vs the per-face reference")
+    s = oracle.Scene()
+    for m, (lo, hi) in objects:
+        s.add_object(*m, tuple(lo), tuple(hi))
+    cam = oracle.camera(centre, (60.0, 60.0), 64, 1.0)
+    per = [oracle.cast_rays(s, cam, rays, normalize=True, object=k) for k in range(3)]
+    want = R.closest_by_centre(per, centre)
+    R.assert_records_equal(oracle.cast_rays(s, cam, rays, normalize=True), want, "the oracle's selection and the numpy one")
+    R.assert_records_equal(gpu.cast_rays(rays, normalize=True).view(oracle.HIT_DTYPE), want, "mixed scene vs the oracle")
+    for k in range(3):
+        R.assert_records_equal(gpu.cast_rays(rays, normalize=True, object=k).view(oracle.HIT_DTYPE), per[k], f"object {k} vs the oracle")
     # the cube among the hierarchies (every face unculled) changes nothing
     three_forms(gpu, rays, 1, "mixed scene, min_faces 1", normalize=(True,),
                 expect={"objects": 3, "faces": 6012, "unculled_faces": 12})
