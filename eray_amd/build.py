@@ -106,10 +106,16 @@ ACCEL_DEV_SOURCES = [os.path.join(CSRC, "accel_build.cpp"), os.path.join(CSRC, "
 ACCEL_DEV_HEADERS = ["accel_build.hpp", "accel_walk.hpp", "accel_margin.hpp", "accel_layout.hpp", "accel_check.hpp"]
 
 
+# tests/cpp/accel_refit_main.cpp (the same flags and sources) and tests/cpp/update_args_main.cpp (headers only)
+REFIT_MAIN = os.path.join(ROOT, "tests", "cpp", "accel_refit_main.cpp")
+UPDATE_ARGS_MAIN = os.path.join(ROOT, "tests", "cpp", "update_args_main.cpp")
+UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "include", "eray_hip.h")]
+
+
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
-    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, accel_walk_main,
-    accel_dev_main).  Plain g++: the
+    the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
+    accel_walk_main, accel_dev_main, accel_refit_main, update_args_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -146,7 +152,8 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
                       ("test_rays", os.path.join(ROOT, "tests", "cpp", "test_rays.cpp")),
                       ("test_accel", os.path.join(ROOT, "tests", "cpp", "test_accel.cpp")),
                       ("test_accel_dev", os.path.join(ROOT, "tests", "cpp", "test_accel_dev.cpp")),
-                      ("test_reach", os.path.join(ROOT, "tests", "cpp", "test_reach.cpp"))):
+                      ("test_reach", os.path.join(ROOT, "tests", "cpp", "test_reach.cpp")),
+                      ("test_update", os.path.join(ROOT, "tests", "cpp", "test_update.cpp"))):
         exe = os.path.join(BIN_DIR, name)
         if force or not _newer(exe, [src, HOST_LIB] + headers):
             run([cxx, *flags, src, "-o", exe, "-L" + LIB_DIR, "-leray_host", *link])
@@ -163,6 +170,16 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     exe = os.path.join(BIN_DIR, "accel_dev_main")
     if force or not _newer(exe, dev_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
         run([cxx, *ACCEL_WALK_FLAGS, *dev_src, "-o", exe])
+    outs.append(exe)
+    # the refit of a device-built hierarchy emulated the same way, and the update's argument checks
+    refit_src = [REFIT_MAIN, *ACCEL_DEV_SOURCES]
+    exe = os.path.join(BIN_DIR, "accel_refit_main")
+    if force or not _newer(exe, refit_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
+        run([cxx, *ACCEL_WALK_FLAGS, *refit_src, "-o", exe])
+    outs.append(exe)
+    exe = os.path.join(BIN_DIR, "update_args_main")
+    if force or not _newer(exe, [UPDATE_ARGS_MAIN, *UPDATE_ARGS_HEADERS]):
+        run([cxx, "-std=c++17", "-O2", "-Wall", UPDATE_ARGS_MAIN, "-o", exe])
     outs.append(exe)
     return outs
 

@@ -140,6 +140,20 @@ class RayAccelInfo(C.Structure):  # eray_ray_accel_info
                 ("unculled_faces", C.c_uint64), ("device_bytes", C.c_uint64), ("build_ms", C.c_float)]
 
 
+UPDATE_DEVICE = 1
+UPDATE_BBOX = 2
+
+
+class ObjectUpdate(C.Structure):  # eray_object_update
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p),
+                ("triangle_count", C.c_uint32), ("flags", C.c_uint32), ("bbox_min", C.c_float * 3),
+                ("bbox_max", C.c_float * 3)]
+
+
+class RayAccelRefitInfo(C.Structure):  # eray_ray_accel_refit_info
+    _fields_ = [("accel", RayAccelInfo), ("refitted", C.c_uint32), ("rebuilt", C.c_uint32)]
+
+
 # eray_ray / eray_ray_hit as numpy records
 RAY_DTYPE = np.dtype([("start", np.float32, 3), ("dir", np.float32, 3)])
 HIT_DTYPE = np.dtype([("object", np.int32), ("face", np.int32), ("position", np.float32, 3),
@@ -199,6 +213,9 @@ SIGNATURES = {
     "eray_scene_set_object_example_material": (C.c_int, [_P, _U, C.POINTER(ExampleMaterial)]),
     "eray_scene_set_object_texel_graph": (C.c_int, [_P, _U, C.POINTER(TexelGraph)]),
     "eray_scene_add_object": (C.c_int, [_P, C.POINTER(Object), C.POINTER(_U)]),
+    "eray_scene_update_object": (C.c_int, [_P, _U, C.POINTER(ObjectUpdate)]),
+    "eray_scene_refit_ray_accel": (C.c_int, [_P, C.POINTER(RayAccelRefitInfo)]),
+    "eray_scene_object_triangle_count": (C.c_int, [_P, _U, C.POINTER(_U)]),
     "eray_camera_size": (C.c_int, [C.POINTER(Camera), C.POINTER(_U), C.POINTER(_U)]),
     "eray_render": (C.c_int, [_P, C.POINTER(RenderParams)]),
     "eray_cast_rays": (C.c_int, [_P, C.POINTER(RaysParams)]),
@@ -258,7 +275,8 @@ DEBUG_SIGNATURES = {
 
 # Entry points a library selected by ERAY_LIB may predate (scripts/rays_bench.py --secondary runs the
 # parent commit's build): absent there, they stay unbound; the product library must have them all.
-_AB_OPTIONAL = {"eray_rays_reach_light"}
+_AB_OPTIONAL = {"eray_rays_reach_light", "eray_scene_update_object", "eray_scene_refit_ray_accel",
+                "eray_scene_object_triangle_count"}
 
 _lib = None
 
@@ -588,6 +606,58 @@ class Context:
         idx = _U()
         self._check(lib().eray_scene_add_object(self._h, C.byref(obj), C.byref(idx)))
         return idx.value
+
+    def object_triangle_count(self, index) -> int:
+        """The face count of object `index` (eray_scene_object_triangle_count)."""
+        n = _U()
+        self._check(lib().eray_scene_object_triangle_count(self._h, index, C.byref(n)))
+        return n.value
+
+    def update_object_device(self, index, pos_ptr, nrm_ptr, uv_ptr, count, flags=UPDATE_DEVICE, bbox=None) -> None:
+        """eray_scene_update_object on raw pointers (None: that array is kept), `count` the object's
+        face count.  With UPDATE_DEVICE (and no UPDATE_BBOX) on an uploaded scene the call only
+        enqueues on the context's stream: the form for graph captures."""
+        lo, hi = bbox if bbox is not None else ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+        u = ObjectUpdate(pos_ptr or None, nrm_ptr or None, uv_ptr or None, count, flags,
+                         (C.c_float * 3)(*lo), (C.c_float * 3)(*hi))
+        self._check(lib().eray_scene_update_object(self._h, index, C.byref(u)))
+
+    def update_object(self, index, positions=None, normals=None, uvs=None, bbox=None) -> None:
+        """New vertex arrays for object `index` in place (eray_scene_update_object): each of
+        positions (T, 9), normals (T, 9), uvs (T, 6) is given or None (kept); all numpy arrays (the
+        host form) or all DeviceArrays (UPDATE_DEVICE).  bbox=(min, max) replaces the bounding box.
+        The face count is the object's."""
+        given = [(a, k) for a, k in ((positions, 9), (normals, 9), (uvs, 6)) if a is not None]
+        device = [isinstance(a, DeviceArray) for a, _ in given]
+        if any(device) and not all(device):
+            raise ValueError("positions / normals / uvs mix DeviceArrays and host arrays")
+        keep, ptrs, counts = [], [], set()
+        for a, k in ((positions, 9), (normals, 9), (uvs, 6)):
+            if a is None:
+                ptrs.append(None)
+            elif isinstance(a, DeviceArray):
+                ptrs.append(a.ptr)
+                counts.add(a.nbytes // (4 * k))
+            else:
+                h = np.ascontiguousarray(a, np.float32).reshape(-1, k)
+                keep.append(h)
+                ptrs.append(h.ctypes.data)
+                counts.add(h.shape[0])
+        if len(counts) > 1:
+            raise ValueError("positions/normals/uvs disagree on the triangle count")
+        flags = (UPDATE_DEVICE if any(device) else 0) | (UPDATE_BBOX if bbox is not None else 0)
+        count = counts.pop() if counts else self.object_triangle_count(index)  # (the box alone)
+        self.update_object_device(index, ptrs[0], ptrs[1], ptrs[2], count, flags, bbox)
+
+    def refit_ray_accel(self) -> dict:
+        """eray_scene_refit_ray_accel: the hierarchy made valid for the current geometry — the
+        device build's topology kept when only update_object happened since (rebuilt == 0), else a
+        device build (rebuilt == 1).  Returns eray_ray_accel_info's fields plus refitted, rebuilt."""
+        info = RayAccelRefitInfo()
+        self._check(lib().eray_scene_refit_ray_accel(self._h, C.byref(info)))
+        out = {name: getattr(info.accel, name) for name, _ in RayAccelInfo._fields_}
+        out["refitted"], out["rebuilt"] = info.refitted, info.rebuilt
+        return out
 
     def render(self, image_width, image_height, row0=0, rows=None, out_rgb=None, out_ppm=None,
                out_face=None, bounces=0, anti_aliasing=0, flags=RENDER_DEFAULT, aa_seed=0, band_rows=0,

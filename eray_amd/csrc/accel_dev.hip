@@ -18,6 +18,10 @@
 //                   inner nodes (make_inner) exactly as accel_layout.hpp lays them out
 //   object_kernel   the Object records
 //
+// accel_refit_device keeps a built topology for moved faces: margin_kernel, refit_check_kernel (the
+// unculled lists are still exact), the same read-back, refit_level_kernel per level over the
+// hierarchy's own index array, object_kernel — no scan, no keys, no sort, no allocation that stays.
+//
 // The host reads back 16 B of counters per covered object after key_kernel (it needs the culled
 // counts to size the node array and lay out the levels); nothing else crosses the bus.
 #include "accel_dev.hpp"
@@ -36,11 +40,8 @@ namespace {
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kWaves = kBlock / 64;
 
-struct DevObj {  // 48 B
-    uint32_t hot_begin, faces, gbegin, block_begin;
-    uint32_t index, C, U, cbase;       // C, U, cbase: the culled / unculled counts, first sorted position
-    uint32_t node_base, full, extra, pad;  // (accel_layout.hpp TreeLayout)
-};
+using DevObj = AccelDevLayout;  // 48 B (owners.hpp: RayAccel keeps the build's for the refit)
+static_assert(sizeof(DevObj) == 48, "uploaded as it stands");
 
 struct DevAcc {  // 64 B; lo starts at all ones, the rest at zero
     unsigned long long lo[3], hi[3], gamma, pad;
@@ -200,6 +201,41 @@ __global__ __launch_bounds__(kBlock) void level_kernel(uint32_t level, uint32_t 
     const DevObj ob = objs[obj0 + blockIdx.y];
     const accel::TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
     accel::level_node(t, level, blockIdx.x * kBlock + threadIdx.x, ids + ob.cbase, ob.gbegin,
+                      reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin, alpha_beta + 2 * (size_t)ob.gbegin, ob.node_base,
+                      ob.gbegin + ob.U, nodes, bounds, hot, index);
+}
+
+// The refit's check of the unculled lists (same grid as margin_kernel; lane k takes the object's
+// k-th unculled slot): the face a slot lists must still be flagged unculled — with the per-object
+// unculled count unchanged (the host compares it) the list is then exactly the unculled set again.
+// The slot's record copy is refreshed; a slot that fails posts the object's status word.
+__global__ __launch_bounds__(kBlock) void refit_check_kernel(const TriHot* __restrict__ tris, const DevObj* __restrict__ objs,
+                                                             uint32_t nobj, const uint32_t* __restrict__ flags,
+                                                             const uint32_t* __restrict__ index, accel::Hot* __restrict__ hot,
+                                                             DevCount* __restrict__ cnt) {
+    const uint32_t o = object_of_block(objs, nobj, blockIdx.x);
+    const DevObj ob = objs[o];
+    const uint32_t k = (blockIdx.x - ob.block_begin) * kBlock + threadIdx.x;
+    if (k >= ob.U) return;  // (U <= faces: the slot is the object's)
+    const uint32_t slot = ob.gbegin + k, f = index[slot];
+    if (f < ob.faces && flags[ob.gbegin + f] != 0u)
+        store_hot(hot + slot, load_hot(tris + ob.hot_begin + f));
+    else
+        atomicOr(&cnt[o].status, 1u);
+}
+
+// level_kernel for the refit: the sorted order of an object is the hierarchy's own index array from
+// its first culled slot (a leaf's slots hold its range of the order, ascending; make_leaf re-sorts
+// them), bias 0.  `index` is read and written — each lane reads its leaves' ranges before it
+// writes them, and no two lanes share a range — so neither pointer is __restrict__.
+__global__ __launch_bounds__(kBlock) void refit_level_kernel(uint32_t level, uint32_t obj0, const TriHot* __restrict__ tris,
+                                                             const DevObj* __restrict__ objs,
+                                                             const double* __restrict__ alpha_beta, accel::Node* nodes,
+                                                             accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
+                                                             uint32_t* index) {
+    const DevObj ob = objs[obj0 + blockIdx.y];
+    const accel::TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
+    accel::level_node(t, level, blockIdx.x * kBlock + threadIdx.x, index + ob.gbegin + ob.U, 0u,
                       reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin, alpha_beta + 2 * (size_t)ob.gbegin, ob.node_base,
                       ob.gbegin + ob.U, nodes, bounds, hot, index);
 }
@@ -372,6 +408,69 @@ hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObj
         TRY(hipGetLastError());
         TRY(hipStreamSynchronize(s));
     }
+    ra.layout = objs;  // (the refit's: accel_refit_device)
+    ra.max_depth = depth;
+    return hipSuccess;
+}
+
+hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, AccelDevInfo* info, bool* kept) {
+    *info = AccelDevInfo{};
+    *kept = false;
+    const std::vector<DevObj>& objs = ra.layout;
+    const uint32_t ncov = (uint32_t)objs.size();
+    if (!ncov) return hipSuccess;
+    const uint32_t F = objs.back().gbegin + objs.back().faces,
+                   blocks = objs.back().block_begin + (objs.back().faces + kBlock - 1) / kBlock;
+    uint64_t P = 0;
+    for (const DevObj& ob : objs) P += ob.C;
+
+    Arena a;
+    const size_t o_objs = a.reserve(sizeof(DevObj) * ncov), o_acc = a.reserve(sizeof(DevAcc) * ncov),
+                 o_cnt = a.reserve(sizeof(DevCount) * ncov), o_flags = a.reserve(4 * (size_t)F), o_ab = a.reserve(16 * (size_t)F),
+                 o_bounds = a.reserve(P ? sizeof(accel::NodeBounds) * ra.node_count : 0);
+    TRY(a.alloc());
+    DevObj* d_objs = a.at<DevObj>(o_objs);
+    DevAcc* d_acc = a.at<DevAcc>(o_acc);
+    DevCount* d_cnt = a.at<DevCount>(o_cnt);
+    uint32_t* d_flags = a.at<uint32_t>(o_flags);
+    double* d_ab = a.at<double>(o_ab);
+
+    std::vector<DevAcc> acc0(ncov);
+    for (DevAcc& x : acc0) x = DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0};
+    TRY(hipMemcpyAsync(d_objs, objs.data(), sizeof(DevObj) * ncov, hipMemcpyHostToDevice, s));
+    TRY(hipMemcpyAsync(d_acc, acc0.data(), sizeof(DevAcc) * ncov, hipMemcpyHostToDevice, s));
+    TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCount) * ncov, s));
+    if (blocks) {
+        margin_kernel<<<blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, reinterpret_cast<double2*>(d_ab), d_acc, d_cnt);
+        TRY(hipGetLastError());
+        refit_check_kernel<<<blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, ra.index, ra.hot, d_cnt);
+        TRY(hipGetLastError());
+    }
+    // the one round trip, the build's: 16 B of counters per covered object
+    std::vector<DevCount> cnt(ncov);
+    TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(DevCount) * ncov, hipMemcpyDeviceToHost, s));
+    TRY(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < ncov; ++i) {
+        if (cnt[i].status || cnt[i].culled != objs[i].C || cnt[i].unculled != objs[i].U) return hipSuccess;  // a class change
+        info->unculled += objs[i].U;
+    }
+    info->nodes = ra.node_count;
+    info->max_depth = ra.max_depth;
+    if (P) {
+        accel::NodeBounds* d_bounds = a.at<accel::NodeBounds>(o_bounds);
+        for (uint32_t level = ra.max_depth; level-- > 0;) {
+            const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
+            for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
+                refit_level_kernel<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes,
+                                                                                             d_bounds, ra.hot, ra.index);
+                TRY(hipGetLastError());
+            }
+        }
+    }
+    object_kernel<<<(ncov + kBlock - 1) / kBlock, kBlock, 0, s>>>(d_objs, ncov, d_acc, ra.objs);
+    TRY(hipGetLastError());
+    TRY(hipStreamSynchronize(s));  // (the temporaries go out of scope)
+    *kept = true;
     return hipSuccess;
 }
 

@@ -34,5 +34,13 @@ struct AccelDevInfo {
 hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObject>& covered, size_t nobj, RayAccel& ra,
                               hipStream_t s, AccelDevInfo* info, const char** refuse);
 
+// Refits a hierarchy that accel_build_device built (ra.layout, ra.max_depth, its four arrays) to
+// the records d_hot now holds, on stream s, and waits for it: the topology, the slots and the
+// unculled lists stay; every margin, box, min_index, record copy and gamma is recomputed by the
+// build's functions.  The same one device-to-host copy as the build.  *kept is false (ra's arrays
+// partly rewritten, not to be used) when some face changed between culled and unculled: the caller
+// rebuilds.  Temporaries (flags, margins, per-node double bounds) are released before it returns.
+hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, AccelDevInfo* info, bool* kept);
+
 }  // namespace gpu
 }  // namespace eray

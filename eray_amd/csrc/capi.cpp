@@ -36,6 +36,9 @@ constexpr uint32_t kUnionRing = 4;  // camera paths whose rectangle unions the h
 struct HostObject {
     std::vector<float> raw;  // T*9 positions | T*9 normals | T*6 uvs
     uint32_t T = 0;
+    // eray_scene_update_object replaced (part of) the geometry from device arrays: the resident raw
+    // array holds it, `raw` does not (refresh_raw reads it back before the scene is uploaded again)
+    bool raw_stale = false;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     eray_material mat{};
     bool example = false;  // color + diffuse from main.rs's graph at the hit texel
@@ -202,6 +205,7 @@ struct eray_ctx {
     Stream fill_stream;
     Event fill_fork, fill_join;
     LaunchCtx lc{nullptr, nullptr, nullptr};
+    Event update_join;  // eray_scene_update_object: the other streams' work so far, waited for by `stream`
 
     // Waits for the context's streams, then releases what the members do not own themselves.
     ~eray_ctx() {
@@ -417,6 +421,31 @@ int sync_scene(eray_ctx* ctx) {
         }
         ctx->desc_dirty = false;
         ++ctx->scene_gen;
+    }
+    return ERAY_OK;
+}
+
+// Brings HostObject::raw up to date for the objects whose geometry eray_scene_update_object took
+// from device arrays (their slices of the resident raw array; synchronises).  Such an object exists
+// only while the geometry is resident: the update uploads the scene first, and every call that
+// marks the geometry dirty comes here before it does.
+int refresh_raw(eray_ctx* ctx) {
+    bool any = false;
+    for (auto& o : ctx->objects) any |= o.raw_stale;
+    if (!any) return ERAY_OK;
+    if (int st = use_device(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t T = ctx->total_tris;
+    size_t begin = 0;
+    for (auto& o : ctx->objects) {
+        if (o.raw_stale && o.T) {
+            const size_t n = o.T;
+            HIP_TRY(ctx, hipMemcpy(o.raw.data(), ctx->d_raw + 9 * begin, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(o.raw.data() + 9 * n, ctx->d_raw + 9 * T + 9 * begin, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(o.raw.data() + 18 * n, ctx->d_raw + 18 * T + 6 * begin, sizeof(float) * 6 * n, hipMemcpyDeviceToHost));
+        }
+        o.raw_stale = false;
+        begin += o.T;
     }
     return ERAY_OK;
 }
@@ -935,6 +964,7 @@ int eray_scene_reset(eray_ctx* ctx) {
     ctx->camera = eray_camera{{0.0f, 0.0f, 0.0f}, {60.0f, 60.0f}, 1024u, 1.0f};
     ctx->geom_dirty = ctx->desc_dirty = true;
     ctx->ray_accel.valid = false;
+    ctx->ray_accel.scene_changed = true;
     return ERAY_OK;
 }
 
@@ -1026,6 +1056,7 @@ int eray_scene_add_object(eray_ctx* ctx, const eray_object* obj, uint32_t* index
     if (total > kMaxSceneTris)
         return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "too many triangles: %llu in the scene (at most %llu)",
                          (unsigned long long)total, (unsigned long long)kMaxSceneTris);
+    if (int st = refresh_raw(ctx)) return st;  // (the upload below rebuilds every slice from the host copies)
     HostObject h;
     h.T = T;
     h.raw.resize((size_t)T * 24);
@@ -1043,6 +1074,99 @@ int eray_scene_add_object(eray_ctx* ctx, const eray_object* obj, uint32_t* index
     if (index) *index = (uint32_t)(ctx->objects.size() - 1);
     ctx->geom_dirty = ctx->desc_dirty = true;
     ctx->ray_accel.valid = false;
+    ctx->ray_accel.scene_changed = true;
+    return ERAY_OK;
+}
+
+// The face count of an object of the scene (what eray_object_update::triangle_count must name).
+int eray_scene_object_triangle_count(eray_ctx* ctx, uint32_t index, uint32_t* count) {
+    if (!ctx || !count) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "null argument");
+    if (index >= ctx->objects.size())
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "object %u out of range (%zu objects)", index, ctx->objects.size());
+    *count = ctx->objects[index].T;
+    return ERAY_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// Orders the context's stream after what the library's other streams hold now (enqueue only; not
+// during a capture, where an event of a stream outside the capture cannot be waited for).  A
+// context on the null stream is never capturing, and asking about the null stream while another
+// stream of the process captures would itself be an illegal call: it is not asked.
+int order_after_side_streams(eray_ctx* ctx) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (ctx->stream) HIP_TRY(ctx, hipStreamIsCapturing(ctx->stream, &capturing));
+    if (capturing != hipStreamCaptureStatusNone) return ERAY_OK;
+    if (!ctx->update_join) HIP_TRY(ctx, ctx->update_join.create(hipEventDisableTiming));
+    for (hipStream_t side : {(hipStream_t)ctx->mc_stream, (hipStream_t)ctx->fill_stream}) {
+        if (!side || side == ctx->stream) continue;
+        HIP_TRY(ctx, hipEventRecord(ctx->update_join, side));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_join, 0));
+    }
+    return ERAY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// New vertex arrays for one object, in place (render.hip tri_update_kernel): the object's slices of
+// the records and of the resident raw array are rewritten on the context's stream.  Everything
+// derived from the geometry per camera is keyed on scene_gen and redone by its next user.  The work
+// of the library's other streams that reads the records (the multi-camera setups on mc_stream, the
+// separate fill's fork) is joined back into the context's stream by the call that starts it, so the
+// kernel's place in that stream orders it after them; outside a capture the call also waits, on
+// the stream, for whatever those streams hold at this point (order_after_side_streams).
+int eray_scene_update_object(eray_ctx* ctx, uint32_t index, const eray_object_update* up) {
+    if (int st = use_device(ctx)) return st;
+    const char* why = "";
+    if (int st = eray::check_update_params(up, index, ctx->objects.size(), index < ctx->objects.size() ? ctx->objects[index].T : 0u,
+                                           &why))
+        return set_error(ctx, st, "eray_scene_update_object: %s", why);
+    if (int st = sync_scene(ctx)) return st;  // (a scene not yet on the device is uploaded first)
+    HostObject& o = ctx->objects[index];
+    const size_t T = o.T, total = ctx->total_tris;
+    size_t begin = 0;
+    for (uint32_t i = 0; i < index; ++i) begin += ctx->objects[i].T;
+    const bool device = (up->flags & ERAY_UPDATE_DEVICE) != 0;
+    if (T && (up->positions || up->normals || up->uvs)) {
+        const float *dp = up->positions, *dn = up->normals, *du = up->uvs;
+        DeviceBuf<float> staged;  // host arrays: uploaded here, read by the kernel, released after a wait
+        if (!device) {
+            const size_t np = dp ? 9 * T : 0, nn = dn ? 9 * T : 0, nu = du ? 6 * T : 0;
+            HIP_TRY(ctx, staged.alloc(np + nn + nu));
+            if (dp) HIP_TRY(ctx, hipMemcpyAsync(staged, dp, sizeof(float) * np, hipMemcpyHostToDevice, ctx->stream));
+            if (dn) HIP_TRY(ctx, hipMemcpyAsync(staged + np, dn, sizeof(float) * nn, hipMemcpyHostToDevice, ctx->stream));
+            if (du) HIP_TRY(ctx, hipMemcpyAsync(staged + np + nn, du, sizeof(float) * nu, hipMemcpyHostToDevice, ctx->stream));
+            if (dp) dp = staged;
+            if (dn) dn = staged + np;
+            if (du) du = staged + np + nn;
+        }
+        if (int st = order_after_side_streams(ctx)) return st;
+        HIP_TRY(ctx, launch_tri_update(dp, dn, du, (uint32_t)T, ctx->d_raw + 9 * begin, ctx->d_raw + 9 * total + 9 * begin,
+                                       ctx->d_raw + 18 * total + 6 * begin, ctx->d_hot + begin, ctx->d_shade + begin,
+                                       ctx->stream));
+        if (device) {
+            o.raw_stale = true;
+        } else {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            // the host copy follows the records once they are written (a failure above leaves both as they were)
+            if (up->positions) std::memcpy(o.raw.data(), up->positions, sizeof(float) * 9 * T);
+            if (up->normals) std::memcpy(o.raw.data() + 9 * T, up->normals, sizeof(float) * 9 * T);
+            if (up->uvs) std::memcpy(o.raw.data() + 18 * T, up->uvs, sizeof(float) * 6 * T);
+        }
+        // positions move the faces: the hierarchy's boxes no longer hold them (its arrays stay for
+        // eray_scene_refit_ray_accel); normals and uvs are not in it
+        if (up->positions) ctx->ray_accel.valid = false;
+        ++ctx->scene_gen;
+    }
+    if (up->flags & ERAY_UPDATE_BBOX) {
+        for (int k = 0; k < 3; ++k) {
+            o.lo[k] = up->bbox_min[k];
+            o.hi[k] = up->bbox_max[k];
+        }
+        ctx->desc_dirty = true;  // (the next call uploads the descriptors: sync_scene)
+    }
     return ERAY_OK;
 }
 
@@ -1368,6 +1492,7 @@ int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel
         ra.min_faces = min_faces;
         ra.node_count = nodes.size();
         ra.slot_count = leaf.size();
+        ra.builder = RayAccel::kHost;
         ra.valid = true;
     }
     out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1375,27 +1500,31 @@ int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel
     return ERAY_OK;
 }
 
-// The same hierarchy built on the context's stream from the resident records (accel_dev.hip): one
-// round trip of 16 B of counters per covered object, no face record leaves the device.
-int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
-    if (int st = use_device(ctx)) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = sync_scene(ctx)) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
-    RayAccel& ra = ctx->ray_accel;
-    ra.drop();
-    if (!min_faces) min_faces = 2 * kRayTile;
+}  // extern "C"
+
+namespace {
+// The objects that get a hierarchy: at least min_faces faces.
+std::vector<AccelDevObject> covered_objects(const eray_ctx* ctx, uint32_t min_faces) {
     std::vector<AccelDevObject> covered;
-    eray_ray_accel_info out{};
     uint32_t begin = 0;
     for (size_t i = 0; i < ctx->objects.size(); ++i) {
         const uint32_t n = ctx->objects[i].T;
-        if (n >= min_faces) {
-            covered.push_back(AccelDevObject{(uint32_t)i, begin, n});
-            ++out.objects;
-            out.faces += n;
-        }
+        if (n >= min_faces) covered.push_back(AccelDevObject{(uint32_t)i, begin, n});
         begin += n;
+    }
+    return covered;
+}
+
+// eray_scene_build_ray_accel_device once the scene is uploaded and the stream idle.
+int build_accel_device(eray_ctx* ctx, uint32_t min_faces, std::chrono::steady_clock::time_point t0, eray_ray_accel_info* info) {
+    RayAccel& ra = ctx->ray_accel;
+    ra.drop();
+    if (!min_faces) min_faces = 2 * kRayTile;
+    const std::vector<AccelDevObject> covered = covered_objects(ctx, min_faces);
+    eray_ray_accel_info out{};
+    for (const AccelDevObject& c : covered) {
+        ++out.objects;
+        out.faces += c.faces;
     }
     if (out.objects) {
         AccelDevInfo dev;
@@ -1410,9 +1539,70 @@ int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ra
         ra.min_faces = min_faces;
         ra.node_count = dev.nodes;
         ra.slot_count = out.faces;
+        ra.builder = RayAccel::kDevice;
         ra.valid = true;
     }
     out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = out;
+    return ERAY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// The same hierarchy built on the context's stream from the resident records (accel_dev.hip): one
+// round trip of 16 B of counters per covered object, no face record leaves the device.
+int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
+    if (int st = use_device(ctx)) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int st = sync_scene(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
+    return build_accel_device(ctx, min_faces, t0, info);
+}
+
+// Makes the hierarchy valid for the current records: the device build's topology is kept when only
+// eray_scene_update_object happened since (accel_dev.hip accel_refit_device), else a device build.
+int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
+    if (int st = use_device(ctx)) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    RayAccel& ra = ctx->ray_accel;
+    if (ra.builder == RayAccel::kNone)
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_scene_refit_ray_accel: the scene has no ray-query hierarchy to refit");
+    if (int st = sync_scene(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the arrays)
+    eray_ray_accel_refit_info out{};
+    // the last build was the device's and covered these objects, with these face counts?
+    // ... and no object was added and the scene not reset since (objs has a record per object of the
+    // build's scene: the arrays fit that scene only)
+    bool same = ra.builder == RayAccel::kDevice && !ra.scene_changed && ra.objs.cap == ctx->objects.size();
+    if (same) {
+        const std::vector<AccelDevObject> covered = covered_objects(ctx, ra.min_faces);
+        same = covered.size() == ra.layout.size();
+        for (size_t i = 0; same && i < covered.size(); ++i)
+            same = covered[i].index == ra.layout[i].index && covered[i].hot_begin == ra.layout[i].hot_begin &&
+                   covered[i].faces == ra.layout[i].faces;
+    }
+    bool kept = false;
+    if (same) {
+        AccelDevInfo dev;
+        ra.valid = false;  // (until the refit has gone through)
+        HIP_TRY(ctx, accel_refit_device(ctx->d_hot, ra, ctx->stream, &dev, &kept));
+        if (kept) {
+            out.accel.objects = out.refitted = (uint32_t)ra.layout.size();
+            out.accel.max_depth = dev.max_depth;
+            out.accel.nodes = dev.nodes;
+            out.accel.faces = ra.slot_count;
+            out.accel.unculled_faces = dev.unculled;
+            out.accel.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
+                                     sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
+            out.accel.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            ra.valid = true;
+        }
+    }
+    if (!kept) {
+        if (int st = build_accel_device(ctx, ra.min_faces, t0, &out.accel)) return st;
+        out.rebuilt = 1;
+    }
     if (info) *info = out;
     return ERAY_OK;
 }

@@ -309,6 +309,11 @@ static_assert(sizeof(ObjectDesc) % 16 == 0 && sizeof(LightDesc) % 16 == 0, "16-B
 // ------------------------------------------------------------- launchers (.hip files) ------
 hipError_t launch_tri_precompute(const float* pos, const float* nrm, const float* uv, uint32_t T,
                                  TriHot* hot, TriShade* shade, hipStream_t s);
+// eray_scene_update_object: the same records for one object's T faces from the caller's arrays
+// (device; null: kept), written to the object's slices hot / shade, the given arrays stored into the
+// object's slices raw_* of the resident raw array in the same pass (render.hip tri_update_kernel).
+hipError_t launch_tri_update(const float* pos, const float* nrm, const float* uv, uint32_t T, float* raw_pos,
+                             float* raw_nrm, float* raw_uv, TriHot* hot, TriShade* shade, hipStream_t s);
 // ------------------------------------------------------------- per-camera setup (setup.hip)
 // Everything a camera change needs before its frame, enqueued on the stream with no host round
 // trip (so a camera path can be graph-replayed): per triangle the culling record (TriCull) and

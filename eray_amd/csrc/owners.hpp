@@ -111,7 +111,15 @@ struct DeviceBuf : Buffer<T, hipFree> {
 // The scene's ray-query hierarchy on the device (accel_walk.hpp; capi.cpp
 // eray_scene_build_ray_accel and eray_scene_build_ray_accel_device): per object its record, the nodes, the leaf-ordered copies of the
 // face records (TriHot bytes) and their original indices.  `valid` falls with any geometry change
-// (a stale tree is never used); the memory is released by drop() or with the owner.
+// (a stale tree is never used; eray_scene_refit_ray_accel makes it valid again); the memory is
+// released by drop() or with the owner.
+// A covered object as the device builder laid it out (accel_dev.hip; 48 B, uploaded as it stands).
+struct AccelDevLayout {
+    uint32_t hot_begin, faces, gbegin, block_begin;
+    uint32_t index, C, U, cbase;           // C, U, cbase: the culled / unculled counts, first sorted position
+    uint32_t node_base, full, extra, pad;  // (accel_layout.hpp TreeLayout)
+};
+
 struct RayAccel {
     DeviceBuf<accel::Object> objs;
     DeviceBuf<accel::Node> nodes;
@@ -121,10 +129,23 @@ struct RayAccel {
     // what the last build covered (eray_debug_ray_accel_check): its min_faces, node and slot counts
     uint32_t min_faces = 0;
     size_t node_count = 0, slot_count = 0;
+    // which builder made it (kNone: never built, or dropped) and, for the device builder, its host-side
+    // layout and depth: what eray_scene_refit_ray_accel needs to rewrite the levels of the same topology
+    enum Builder : uint32_t { kNone = 0, kHost = 1, kDevice = 2 };
+    Builder builder = kNone;
+    std::vector<AccelDevLayout> layout;
+    uint32_t max_depth = 0;
+    // eray_scene_add_object or eray_scene_reset happened since the build: `objs` holds a record per
+    // object of the scene as it was, so the arrays fit the old scene only — a refit rebuilds
+    bool scene_changed = false;
     void drop() {
         valid = false;
         min_faces = 0;
         node_count = slot_count = 0;
+        builder = kNone;
+        layout.clear();
+        max_depth = 0;
+        scene_changed = false;
         (void)objs.release();
         (void)nodes.release();
         (void)hot.release();

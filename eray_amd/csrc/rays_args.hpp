@@ -1,7 +1,7 @@
-// rays_args.hpp — eray_cast_rays' and eray_rays_reach_light's argument validation
-// (include/eray_hip.h states the rules): plain host code with no HIP call, so capi.cpp and the
-// stand-alone checkers (tests/cpp/rays_args_main.cpp, tests/cpp/reach_args_main.cpp, built with
-// the host sanitizers) share it.
+// rays_args.hpp — eray_cast_rays', eray_rays_reach_light's and eray_scene_update_object's argument
+// validation (include/eray_hip.h states the rules): plain host code with no HIP call, so capi.cpp
+// and the stand-alone checkers (tests/cpp/rays_args_main.cpp, tests/cpp/reach_args_main.cpp,
+// tests/cpp/update_args_main.cpp, built with the host sanitizers) share it.
 #pragma once
 
 #include <stddef.h>
@@ -43,6 +43,22 @@ inline int check_reach_params(const eray_reach_params* rp, const char** why) {
     if (rp->count && !rp->rays) return *why = "rays is null", ERAY_E_INVALID_ARGUMENT;
     if (rp->count && !rp->targets) return *why = "targets is null", ERAY_E_INVALID_ARGUMENT;
     if (rp->count && !rp->out) return *why = "out is null", ERAY_E_INVALID_ARGUMENT;
+    return ERAY_OK;
+}
+
+// The same for eray_scene_update_object against a scene of `nobj` objects whose object `index` (when
+// it is one) has `faces` faces: ERAY_OK when the update can be applied.
+inline int check_update_params(const eray_object_update* up, uint32_t index, size_t nobj, uint32_t faces, const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!up) return *why = "update is null", ERAY_E_INVALID_ARGUMENT;
+    if (index >= nobj) return *why = "object_index is not an object of the scene", ERAY_E_INVALID_ARGUMENT;
+    if (up->flags & ~(ERAY_UPDATE_DEVICE | ERAY_UPDATE_BBOX)) return *why = "unknown update flags", ERAY_E_INVALID_ARGUMENT;
+    if (up->triangle_count != faces)
+        return *why = "triangle_count is not the object's (an update keeps the face count and order)", ERAY_E_INVALID_ARGUMENT;
+    if (!up->positions && !up->normals && !up->uvs && !(up->flags & ERAY_UPDATE_BBOX))
+        return *why = "positions, normals and uvs are all null without ERAY_UPDATE_BBOX", ERAY_E_INVALID_ARGUMENT;
     return ERAY_OK;
 }
 

@@ -112,6 +112,75 @@ __global__ void __launch_bounds__(256) tri_precompute_kernel(const float* __rest
     shade[i].s3 = make_float4(U[3], U[4], U[5], 0.0f);
 }
 
+// eray_scene_update_object: tri_precompute_kernel for one object's faces whose vertex arrays are
+// replaced in place.  pos / nrm / uv: the caller's arrays (T x 9, T x 9, T x 6; null: kept, not
+// read); raw_*: the object's slices of the resident raw array; hot / shade: its slices of the
+// records.  One face per lane, 256 faces per workgroup.  A workgroup's faces are one contiguous run
+// of each input (256 x 36 B, 256 x 24 B), so the run is read with consecutive lanes on consecutive
+// words — not 36 B apart per lane — and each word goes, in the same pass, to the resident raw array
+// (consecutive again) and to LDS; the lanes then pick their own face's words out of LDS (word
+// strides 9 and 6: conflict-free and 2-way) and compute the records with tri_precompute_kernel's
+// operations.  Record stores are whole 16-B words; the one word of TriShade that mixes normals and
+// uvs (s2) keeps the other array's part from the record when only one of the two is given.
+__global__ void __launch_bounds__(256) tri_update_kernel(const float* __restrict__ pos, const float* __restrict__ nrm,
+                                                         const float* __restrict__ uv, uint32_t T,
+                                                         float* __restrict__ raw_pos, float* __restrict__ raw_nrm,
+                                                         float* __restrict__ raw_uv, TriHot* __restrict__ hot,
+                                                         TriShade* __restrict__ shade) {
+    __shared__ float s_w[256 * 9];
+    const uint32_t f0 = blockIdx.x * 256u, tid = threadIdx.x;
+    const uint32_t nf = T - f0 < 256u ? T - f0 : 256u;  // (the grid covers T: f0 < T)
+    const uint32_t i = f0 + tid;
+    const bool live = tid < nf;
+    // one array's run through LDS and into the resident copy (workgroup-uniform control flow)
+    auto stage = [&](const float* __restrict__ src, float* __restrict__ dst, uint32_t per) {
+        const size_t base = (size_t)per * f0;
+        const uint32_t words = per * nf;
+        __syncthreads();  // (the previous array's words have been picked up)
+        for (uint32_t w = tid; w < words; w += 256u) {
+            const float v = src[base + w];
+            s_w[w] = v;
+            dst[base + w] = v;
+        }
+        __syncthreads();
+    };
+    if (pos) {
+        stage(pos, raw_pos, 9u);
+        if (live) {
+            const float* P = s_w + 9u * tid;
+            f3 a = mk3(P[0], P[1], P[2]), b = mk3(P[3], P[4], P[5]), c = mk3(P[6], P[7], P[8]);
+            f3 e1 = sub(b, a), e2 = sub(c, a);
+            f3 n = cross(e1, e2);
+            hot[i].q0 = make_float4(e1.x, e1.y, e1.z, e2.x);
+            hot[i].q1 = make_float4(e2.y, e2.z, n.x, n.y);
+            hot[i].q2 = make_float4(n.z, a.x, a.y, a.z);
+        }
+    }
+    if (!nrm && !uv) return;
+    float4 s2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (live && (!nrm || !uv)) s2 = shade[i].s2;
+    if (nrm) {
+        stage(nrm, raw_nrm, 9u);
+        if (live) {
+            const float* N = s_w + 9u * tid;
+            shade[i].s0 = make_float4(N[0], N[1], N[2], N[3]);
+            shade[i].s1 = make_float4(N[4], N[5], N[6], N[7]);
+            s2.x = N[8];
+        }
+    }
+    if (uv) {
+        stage(uv, raw_uv, 6u);
+        if (live) {
+            const float* U = s_w + 6u * tid;
+            s2.y = U[0];
+            s2.z = U[1];
+            s2.w = U[2];
+            shade[i].s3 = make_float4(U[3], U[4], U[5], 0.0f);
+        }
+    }
+    if (live) shade[i].s2 = s2;
+}
+
 struct Bundle {  // a wave's pixel rectangle in viewport coordinates
     float xlo, xhi, ylo, yhi;
 };
@@ -1799,6 +1868,13 @@ hipError_t launch_tri_precompute(const float* pos, const float* nrm, const float
                                  TriHot* hot, TriShade* shade, hipStream_t s) {
     if (!T) return hipSuccess;
     tri_precompute_kernel<<<(T + 255) / 256, 256, 0, s>>>(pos, nrm, uv, T, hot, shade);
+    return hipGetLastError();
+}
+
+hipError_t launch_tri_update(const float* pos, const float* nrm, const float* uv, uint32_t T, float* raw_pos,
+                             float* raw_nrm, float* raw_uv, TriHot* hot, TriShade* shade, hipStream_t s) {
+    if (!T || (!pos && !nrm && !uv)) return hipSuccess;
+    tri_update_kernel<<<(T + 255) / 256, 256, 0, s>>>(pos, nrm, uv, T, raw_pos, raw_nrm, raw_uv, hot, shade);
     return hipGetLastError();
 }
 

@@ -250,6 +250,24 @@ Engine::Engine(std::pair<uint32_t, uint32_t> size, uint32_t bounces, uint32_t an
     aa_seed_ = ((uint64_t)rd() << 32) | rd();
 }
 
+// The faces of an object as the C-ABI takes them: T x 9 positions, T x 9 normals, T x 6 uvs.
+static void flatten(const Object<Built>& o, std::vector<float>& pos, std::vector<float>& nrm, std::vector<float>& uv) {
+    const size_t T = o.faces.size();
+    pos.resize(9 * T), nrm.resize(9 * T), uv.resize(6 * T);
+    for (size_t i = 0; i < T; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const Triangle& t = o.faces[i];
+            pos[9 * i + 3 * k + 0] = t.pos[k].x;
+            pos[9 * i + 3 * k + 1] = t.pos[k].y;
+            pos[9 * i + 3 * k + 2] = t.pos[k].z;
+            nrm[9 * i + 3 * k + 0] = t.normal[k].x;
+            nrm[9 * i + 3 * k + 1] = t.normal[k].y;
+            nrm[9 * i + 3 * k + 2] = t.normal[k].z;
+            uv[6 * i + 2 * k + 0] = t.uv[k][0];
+            uv[6 * i + 2 * k + 1] = t.uv[k][1];
+        }
+}
+
 void Engine::upload() {
     Device& d = Device::current();
     eray_ctx* c = d.ctx();
@@ -266,19 +284,8 @@ void Engine::upload() {
     }
     for (Object<Built>& o : scene_.objects_) {
         const size_t T = o.faces.size();
-        std::vector<float> pos(9 * T), nrm(9 * T), uv(6 * T);
-        for (size_t i = 0; i < T; ++i)
-            for (int k = 0; k < 3; ++k) {
-                const Triangle& t = o.faces[i];
-                pos[9 * i + 3 * k + 0] = t.pos[k].x;
-                pos[9 * i + 3 * k + 1] = t.pos[k].y;
-                pos[9 * i + 3 * k + 2] = t.pos[k].z;
-                nrm[9 * i + 3 * k + 0] = t.normal[k].x;
-                nrm[9 * i + 3 * k + 1] = t.normal[k].y;
-                nrm[9 * i + 3 * k + 2] = t.normal[k].z;
-                uv[6 * i + 2 * k + 0] = t.uv[k][0];
-                uv[6 * i + 2 * k + 1] = t.uv[k][1];
-            }
+        std::vector<float> pos, nrm, uv;
+        flatten(o, pos, nrm, uv);
         eray_object eo{};
         eo.positions = pos.data();
         eo.normals = nrm.data();
@@ -323,6 +330,40 @@ Engine::RayAccelInfo Engine::build_ray_accel(uint32_t min_faces, bool on_device)
     d.check(on_device ? eray_scene_build_ray_accel_device(d.ctx(), min_faces, &i)
                       : eray_scene_build_ray_accel(d.ctx(), min_faces, &i));
     return RayAccelInfo{i.objects, i.max_depth, i.nodes, i.faces, i.unculled_faces, i.device_bytes, i.build_ms};
+}
+
+void Engine::update_object(size_t index, const Object<Built>& object) {
+    Device& d = Device::current();
+    if (scene_.dirty_) upload();
+    if (index >= scene_.objects_.size() || object.faces.size() != scene_.objects_[index].faces.size())
+        throw Failure(ERAY_E_INVALID_ARGUMENT, "Engine::update_object: not an object of the scene, or another face count");
+    std::vector<float> pos, nrm, uv;
+    flatten(object, pos, nrm, uv);
+    eray_object_update u{};
+    u.positions = pos.data();
+    u.normals = nrm.data();
+    u.uvs = uv.data();
+    u.triangle_count = (uint32_t)object.faces.size();
+    u.flags = ERAY_UPDATE_BBOX;
+    u.bbox_min[0] = object.bbox[0].x, u.bbox_min[1] = object.bbox[0].y, u.bbox_min[2] = object.bbox[0].z;
+    u.bbox_max[0] = object.bbox[1].x, u.bbox_max[1] = object.bbox[1].y, u.bbox_max[2] = object.bbox[1].z;
+    d.check(eray_scene_update_object(d.ctx(), (uint32_t)index, &u));
+    Object<Built>& mine = scene_.objects_[index];  // (a later upload sends the new geometry; the material stays)
+    mine.vertices = object.vertices;
+    mine.normals = object.normals;
+    mine.uvs = object.uvs;
+    mine.faces = object.faces;
+    mine.bbox = object.bbox;
+}
+
+Engine::RayAccelRefitInfo Engine::refit_ray_accel() {
+    Device& d = Device::current();
+    if (scene_.dirty_) upload();
+    eray_ray_accel_refit_info r{};
+    d.check(eray_scene_refit_ray_accel(d.ctx(), &r));
+    const eray_ray_accel_info& i = r.accel;
+    return RayAccelRefitInfo{{i.objects, i.max_depth, i.nodes, i.faces, i.unculled_faces, i.device_bytes, i.build_ms},
+                             r.refitted, r.rebuilt != 0};
 }
 
 void Engine::drop_ray_accel() {

@@ -164,6 +164,24 @@ public:
     };
     RayAccelInfo build_ray_accel(uint32_t min_faces = 0, bool on_device = false);
     void drop_ray_accel();
+    // New geometry for object `index` of the scene in place (eray_scene_update_object): the faces
+    // (positions, normals, uvs) and the bounding box of `object` replace the scene object's; the
+    // face count must be the same, the scene object's material, the lights and the other objects
+    // stay.  Unlike scene(), this does not mark the scene changed: nothing else is uploaded again.
+    // Every later render and query answers as for a scene built with the new object.  A hierarchy
+    // is not used again until refit_ray_accel or build_ray_accel.  Failure with
+    // ERAY_E_INVALID_ARGUMENT for an index that is no object or another face count.
+    void update_object(size_t index, const Object<Built>& object);
+    // The hierarchy made valid for the current geometry (eray_scene_refit_ray_accel): after
+    // update_object alone, on a device-built hierarchy, the tree's topology is kept and its boxes,
+    // margins and face copies are recomputed (the same hits; pruning weakens as the mesh moves away
+    // from the geometry the tree was split for); otherwise it is rebuilt on the device.
+    struct RayAccelRefitInfo {
+        RayAccelInfo accel;
+        uint32_t refitted;  // objects whose topology was kept
+        bool rebuilt;
+    };
+    RayAccelRefitInfo refit_ray_accel();
     // The anti-aliasing jitter stream's key (eray_render_params::aa_seed).  The reference draws
     // from the OS-seeded thread_rng; a new Engine picks a random seed likewise, and fixing it
     // makes anti-aliased renders reproducible.

@@ -468,6 +468,85 @@ int eray_scene_drop_ray_accel(eray_ctx* ctx);
 #define ERAY_HAS_RAY_ACCEL_DEVICE 1
 int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info /* may be NULL */);
 
+/* New vertex data for an object of the scene, in place: the face count and order stay (face k of
+ * the arrays replaces face k), and so do the material, the lights, the camera and every other
+ * object.  Each of positions / normals / uvs is given or NULL (kept).  Afterwards every entry point
+ * answers, bit for bit, as a fresh context would that had received the same scene with the new
+ * arrays through eray_scene_add_object: one kernel (one face per lane) derives the object's slice
+ * of the face records from the given arrays with add_object's own f32 operations and stores the
+ * arrays into the library's resident copy in the same pass.
+ *
+ * With ERAY_UPDATE_DEVICE the arrays are device pointers, and without ERAY_UPDATE_BBOX such a call
+ * on a scene that is already on the device only enqueues that kernel on the context's stream — no
+ * copy, no wait — so it can be captured into a HIP graph together with a following eray_cast_rays;
+ * the arrays are read when the kernel runs.  With host pointers, or with ERAY_UPDATE_BBOX (bbox_min
+ * / bbox_max replace the object's bounding box; the descriptors are uploaded again), the call may
+ * synchronise.  Per-camera setups, screen bins and captured frame graphs are redone by the next
+ * call that needs them.  An update that gives positions marks the ray-query hierarchy not valid —
+ * queries run as without one, as after eray_scene_add_object — but keeps its arrays for
+ * eray_scene_refit_ray_accel below; an update of normals and / or uvs leaves it valid (it holds
+ * positions' records only).
+ *
+ * REPLAYS.  Replaying a graph that holds a captured update rewrites the face records without any
+ * call into the library, so nothing the library derives from the geometry learns of it.  The
+ * queries captured in the same graph, and later ray queries that use no hierarchy, read the new
+ * records.  A later eray_render (its per-camera setup, bins and frame graphs) and a hierarchy that
+ * was refitted or built before the replay still describe the geometry of the last direct call and
+ * would answer for it silently.  After replays, make one direct eray_scene_update_object call with
+ * the current arrays (and eray_scene_refit_ray_accel, if a hierarchy is in use) before rendering or
+ * querying through a hierarchy.
+ *
+ * Errors (ERAY_E_INVALID_ARGUMENT, nothing changed): update NULL, an index that is not an object of
+ * the scene, a triangle_count that is not the object's (eray_scene_object_triangle_count returns
+ * it), unknown flags, all three pointers NULL without ERAY_UPDATE_BBOX.  Present in builds that
+ * define ERAY_HAS_OBJECT_UPDATE. */
+#define ERAY_HAS_OBJECT_UPDATE 1
+#define ERAY_UPDATE_DEVICE 1u       /* positions / normals / uvs are device pointers            */
+#define ERAY_UPDATE_BBOX 2u         /* bbox_min / bbox_max replace the object's bounding box    */
+typedef struct eray_object_update {    /*                                                56 B */
+    const float* positions;         /* offset 0:  T x 9 or NULL: keep                        */
+    const float* normals;           /* offset 8:  T x 9 or NULL: keep                        */
+    const float* uvs;               /* offset 16: T x 6 or NULL: keep                        */
+    uint32_t triangle_count;        /* offset 24: must equal the object's T                  */
+    uint32_t flags;                 /* offset 28: ERAY_UPDATE_*                              */
+    float bbox_min[3], bbox_max[3]; /* offset 32, 44: read with ERAY_UPDATE_BBOX             */
+} eray_object_update;
+int eray_scene_update_object(eray_ctx* ctx, uint32_t object_index, const eray_object_update* update);
+/* The face count of object object_index, as eray_scene_add_object received it.  Errors: a NULL
+ * argument or an index that is not an object of the scene (ERAY_E_INVALID_ARGUMENT). */
+int eray_scene_object_triangle_count(eray_ctx* ctx, uint32_t object_index, uint32_t* count);
+
+/* Makes the ray-query hierarchy valid for the current geometry, with the min_faces of the last
+ * build.  When that build was eray_scene_build_ray_accel_device and only eray_scene_update_object
+ * happened since (no eray_scene_add_object, of however small an object, and no eray_scene_reset;
+ * the covered objects and their face counts are the build's), the TOPOLOGY IS KEPT:
+ * on the context's stream the margins of every covered face are recomputed, a check pass confirms
+ * that each object's unculled list is still exactly the faces without a provable margin (and
+ * refreshes their record copies), the host reads back the same 16 bytes per covered object as the
+ * build — the one round trip — and the levels are rewritten deepest first from the hierarchy's own
+ * leaf-ordered index array: every leaf's faces, box, margins and min_index, every inner node's box,
+ * margins and child order, every object's gamma, by the build's own functions.  Queries are exact
+ * as after a build: the first passing face by index, the same u, v, t bits.  What a refit keeps is
+ * the SPLIT, which is the old geometry's: the boxes grow as the mesh moves away from it and rays
+ * prune less.  Measured on MI355X (scripts/rays_update_bench.py): update + refit
+ * takes 0.38 ms at 69,451 faces and 0.63 ms at 1M against 0.90 ms and 1.61 ms for update + device
+ * build; after a smooth displacement of 1 % or 5 % of the mesh radius 2^20 incoherent rays take no
+ * longer through the refitted tree than through a rebuilt one, after 20 % about 2 % longer.
+ * Otherwise — a face changed class in either direction, the last build was the host's, an object
+ * was added or the scene reset, or the covered set changed — the call rebuilds with the device
+ * builder and reports rebuilt = 1.  No persistent device array is added: device_bytes is the build's; the
+ * per-node double bounds live for the duration of the call.  Synchronous like the builds.  Errors:
+ * ERAY_E_INVALID_ARGUMENT when no hierarchy was built or it was dropped.  Present in builds that
+ * define ERAY_HAS_RAY_ACCEL_REFIT. */
+#define ERAY_HAS_RAY_ACCEL_REFIT 1
+typedef struct eray_ray_accel_refit_info {  /*                                           56 B */
+    eray_ray_accel_info accel;      /* offset 0:  the hierarchy as it now stands; build_ms: this
+                                                  call's host wall time                      */
+    uint32_t refitted;              /* offset 48: covered objects whose topology was kept    */
+    uint32_t rebuilt;               /* offset 52: 1: the call fell back to a full device build */
+} eray_ray_accel_refit_info;
+int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info /* may be NULL */);
+
 /* Engine::reaches_light (engine.rs:218-228) for shadow rays the caller supplies: "does this point
  * see that point" for light baking, visibility probes and a caller's own shading.  Per ray i:
  * dist = |targets[i] - start|; the objects are taken in scene order and the FIRST object whose
