@@ -109,13 +109,15 @@ ACCEL_DEV_HEADERS = ["accel_build.hpp", "accel_walk.hpp", "accel_margin.hpp", "a
 # tests/cpp/accel_refit_main.cpp (the same flags and sources) and tests/cpp/update_args_main.cpp (headers only)
 REFIT_MAIN = os.path.join(ROOT, "tests", "cpp", "accel_refit_main.cpp")
 UPDATE_ARGS_MAIN = os.path.join(ROOT, "tests", "cpp", "update_args_main.cpp")
+# tests/cpp/accel_refit_async_main.cpp: the refit on the stream, the same flags and sources
+REFIT_ASYNC_MAIN = os.path.join(ROOT, "tests", "cpp", "accel_refit_async_main.cpp")
 UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "include", "eray_hip.h")]
 
 
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
     the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
-    accel_walk_main, accel_dev_main, accel_refit_main, update_args_main).  Plain g++: the
+    accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_async_main, update_args_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -176,6 +178,11 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     exe = os.path.join(BIN_DIR, "accel_refit_main")
     if force or not _newer(exe, refit_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
         run([cxx, *ACCEL_WALK_FLAGS, *refit_src, "-o", exe])
+    outs.append(exe)
+    async_src = [REFIT_ASYNC_MAIN, *ACCEL_DEV_SOURCES]
+    exe = os.path.join(BIN_DIR, "accel_refit_async_main")
+    if force or not _newer(exe, async_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
+        run([cxx, *ACCEL_WALK_FLAGS, *async_src, "-o", exe])
     outs.append(exe)
     exe = os.path.join(BIN_DIR, "update_args_main")
     if force or not _newer(exe, [UPDATE_ARGS_MAIN, *UPDATE_ARGS_HEADERS]):

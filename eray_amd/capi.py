@@ -160,6 +160,11 @@ HIT_DTYPE = np.dtype([("object", np.int32), ("face", np.int32), ("position", np.
                       ("normal", np.float32, 3), ("uv", np.float32, 2), ("u", np.float32), ("v", np.float32)])
 
 
+class RayAccelRefitStatus(C.Structure):  # eray_ray_accel_refit_status
+    _fields_ = [("refits", C.c_uint32), ("covered", C.c_uint32), ("kept", C.c_uint32), ("fell_back", C.c_uint32),
+                ("workspace_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class FrameRing(C.Structure):  # eray_frame_ring
     _fields_ = [("slots", C.c_uint32), ("frames_per_launch", C.c_uint32), ("rgb_stride", C.c_uint64),
                 ("ppm_stride", C.c_uint64), ("face_stride", C.c_uint64)]
@@ -215,6 +220,8 @@ SIGNATURES = {
     "eray_scene_add_object": (C.c_int, [_P, C.POINTER(Object), C.POINTER(_U)]),
     "eray_scene_update_object": (C.c_int, [_P, _U, C.POINTER(ObjectUpdate)]),
     "eray_scene_refit_ray_accel": (C.c_int, [_P, C.POINTER(RayAccelRefitInfo)]),
+    "eray_scene_refit_ray_accel_async": (C.c_int, [_P]),
+    "eray_scene_ray_accel_refit_status": (C.c_int, [_P, C.POINTER(RayAccelRefitStatus)]),
     "eray_scene_object_triangle_count": (C.c_int, [_P, _U, C.POINTER(_U)]),
     "eray_camera_size": (C.c_int, [C.POINTER(Camera), C.POINTER(_U), C.POINTER(_U)]),
     "eray_render": (C.c_int, [_P, C.POINTER(RenderParams)]),
@@ -271,12 +278,14 @@ DEBUG_SIGNATURES = {
     "eray_debug_plan_verdict": (C.c_int, [C.POINTER(C.c_int32), _U, _U]),
     "eray_debug_gather_replan": (C.c_int, [_U, _U, C.c_uint64, _U, C.c_uint64]),
     "eray_debug_ray_accel_check": (C.c_int, [_P, C.c_char_p, _U]),
+    "eray_debug_ray_accel_arrays": (C.c_int, [_P, _U, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "eray_debug_set_refit_top_levels": (C.c_int, [_P, C.c_int]),
 }
 
 # Entry points a library selected by ERAY_LIB may predate (scripts/rays_bench.py --secondary runs the
 # parent commit's build): absent there, they stay unbound; the product library must have them all.
 _AB_OPTIONAL = {"eray_rays_reach_light", "eray_scene_update_object", "eray_scene_refit_ray_accel",
-                "eray_scene_object_triangle_count"}
+                "eray_scene_object_triangle_count", "eray_scene_refit_ray_accel_async", "eray_scene_ray_accel_refit_status"}
 
 _lib = None
 
@@ -658,6 +667,38 @@ class Context:
         out = {name: getattr(info.accel, name) for name, _ in RayAccelInfo._fields_}
         out["refitted"], out["rebuilt"] = info.refitted, info.rebuilt
         return out
+
+    def refit_ray_accel_async(self) -> None:
+        """eray_scene_refit_ray_accel_async: the kept-topology refit of a device-built hierarchy enqueued
+        on the context's stream — after its first call outside a capture no copy, no wait, no
+        allocation, so it is captured with update_object_device before it and the queries after it.  The
+        device decides per covered object; refit_status() tells.  Never rebuilds: ErayError
+        (E_INVALID_ARGUMENT) where refit_ray_accel would."""
+        self._check(lib().eray_scene_refit_ray_accel_async(self._h))
+
+    def refit_status(self) -> dict:
+        """eray_scene_ray_accel_refit_status (waits for the stream): refits, covered, kept, fell_back,
+        workspace_bytes."""
+        st = RayAccelRefitStatus()
+        self._check(lib().eray_scene_ray_accel_refit_status(self._h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in RayAccelRefitStatus._fields_ if name != "reserved"}
+
+    def ray_accel_arrays(self) -> dict:
+        """eray_debug_ray_accel_arrays (diagnostics): the hierarchy's device arrays as bytes —
+        objs, nodes, hot, index."""
+        out = {}
+        for which, name in enumerate(("objs", "nodes", "hot", "index")):
+            n = C.c_size_t()
+            self._check(lib().eray_debug_ray_accel_arrays(self._h, which, None, 0, C.byref(n)))
+            buf = C.create_string_buffer(max(n.value, 1))
+            self._check(lib().eray_debug_ray_accel_arrays(self._h, which, buf, n.value, C.byref(n)))
+            out[name] = buf.raw[:n.value]
+        return out
+
+    def set_refit_top_levels(self, on: bool) -> None:
+        """eray_debug_set_refit_top_levels (diagnostics): the async refit's upper levels in one launch
+        (the default) or a launch per level; the same bytes."""
+        self._check(lib().eray_debug_set_refit_top_levels(self._h, 1 if on else 0))
 
     def render(self, image_width, image_height, row0=0, rows=None, out_rgb=None, out_ppm=None,
                out_face=None, bounces=0, anti_aliasing=0, flags=RENDER_DEFAULT, aa_seed=0, band_rows=0,

@@ -21,6 +21,9 @@
 // accel_refit_device keeps a built topology for moved faces: margin_kernel, refit_check_kernel (the
 // unculled lists are still exact), the same read-back, refit_level_kernel per level over the
 // hierarchy's own index array, object_kernel — no scan, no keys, no sort, no allocation that stays.
+// accel_refit_enqueue is that refit with the host taken out (a persistent workspace, the verdict by
+// refit_object_kernel, the levels of at most kBlock nodes by refit_top_levels_kernel in one launch):
+// kernels on the stream only, so that a graph can hold it.
 //
 // The host reads back 16 B of counters per covered object after key_kernel (it needs the culled
 // counts to size the node array and lay out the levels); nothing else crosses the bus.
@@ -254,6 +257,60 @@ __global__ __launch_bounds__(kBlock) void object_kernel(const DevObj* __restrict
     out[ob.index] = r;
 }
 
+// ---- the refit on the stream (accel_refit_enqueue): nothing below is read back by the host ----
+
+// The accumulators' and counters' start values, per covered object (DevAcc: lo all ones, the rest 0).
+__global__ __launch_bounds__(kBlock) void refit_reset_kernel(DevAcc* __restrict__ acc, DevCount* __restrict__ cnt, uint32_t nobj) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= nobj) return;
+    acc[o] = DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0};
+    cnt[o] = DevCount{0, 0, 0, 0};
+}
+
+// refit_level_kernel's levels below first_deep in one launch: one workgroup per covered object
+// (obj0 + blockIdx.x), lane j the level's node j, deepest first.  An inner node reads the nodes and
+// bounds its children's lanes stored one level earlier, through global memory.  s_barrier waits for
+// no counter, and for a workgroup-scope fence the compiler emits no vector-memory wait here, so
+// every wave drains its own stores (s_waitcnt vmcnt(0)) before it joins the barrier; the readers
+// are waves of the same workgroup — the same CU, whose L1 the stores went through — so no
+// agent-scope acquire is needed, and nodes / bounds / index carry no __restrict__, so the compiler
+// neither moves nor keeps a load across the fence in __syncthreads().  The bytes are those of the
+// per-level passes: the same level_node per (level, lane), each level complete before the next.
+__global__ __launch_bounds__(kBlock) void refit_top_levels_kernel(uint32_t first_deep, uint32_t obj0, const TriHot* __restrict__ tris,
+                                                                  const DevObj* __restrict__ objs,
+                                                                  const double* __restrict__ alpha_beta, accel::Node* nodes,
+                                                                  accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
+                                                                  uint32_t* index) {
+    static_assert(kBlock == accel::kTopBlock, "a level of at most kTopBlock nodes per workgroup");
+    const DevObj ob = objs[obj0 + blockIdx.x];
+    const accel::TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
+    for (uint32_t level = first_deep; level-- > 0;) {  // (workgroup-uniform: every lane meets every barrier)
+        accel::level_node(t, level, threadIdx.x, index + ob.gbegin + ob.U, 0u, reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin,
+                          alpha_beta + 2 * (size_t)ob.gbegin, ob.node_base, ob.gbegin + ob.U, nodes, bounds, hot, index);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        __syncthreads();
+    }
+}
+
+// The verdict the synchronous refit takes on the host, taken here: per covered object the counters
+// against the layout (accel::refit_keeps), the Object record written accordingly (object_kernel's
+// on a pass, has = 0 otherwise), the verdict stored; one lane counts the refit.
+__global__ __launch_bounds__(kBlock) void refit_object_kernel(const DevObj* __restrict__ objs, uint32_t nobj,
+                                                              const DevAcc* __restrict__ acc, const DevCount* __restrict__ cnt,
+                                                              accel::Object* __restrict__ out, uint32_t* __restrict__ verdict,
+                                                              uint32_t* refits) {
+    const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
+    if (o == 0) atomicAdd(refits, 1u);
+    if (o >= nobj) return;
+    const DevObj ob = objs[o];
+    const DevCount c = cnt[o];
+    const bool keeps = accel::refit_keeps(c.culled, c.unculled, c.status, ob.C, ob.U);
+    out[ob.index] = accel::refit_object(keeps, ob.C, ob.U, ob.node_base, ob.gbegin, keeps && ob.C ? dec(acc[o].gamma) : 0.0);
+    verdict[o] = keeps ? 1u : 0u;
+}
+
 // one allocation carved into aligned pieces
 struct Arena {
     DeviceBuf<unsigned char> mem;
@@ -471,6 +528,104 @@ hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, 
     TRY(hipGetLastError());
     TRY(hipStreamSynchronize(s));  // (the temporaries go out of scope)
     *kept = true;
+    return hipSuccess;
+}
+
+hipError_t accel_refit_workspace(RayAccel& ra, hipStream_t s) {
+    RefitWorkspace& ws = ra.refit;
+    ws.release();
+    const std::vector<DevObj>& objs = ra.layout;
+    const uint32_t ncov = (uint32_t)objs.size();
+    if (!ncov) return hipSuccess;
+    const uint32_t F = objs.back().gbegin + objs.back().faces;
+    uint64_t P = 0;
+    uint32_t max_full = 0;
+    for (const DevObj& ob : objs) {
+        P += ob.C;
+        if (ob.C) max_full = std::max(max_full, ob.full);
+    }
+    Arena a;
+    ws.o_objs = a.reserve(sizeof(DevObj) * ncov);
+    ws.o_acc = a.reserve(sizeof(DevAcc) * ncov);
+    ws.o_cnt = a.reserve(sizeof(DevCount) * ncov);
+    ws.o_flags = a.reserve(4 * (size_t)F);
+    ws.o_ab = a.reserve(16 * (size_t)F);
+    ws.o_bounds = a.reserve(P ? sizeof(accel::NodeBounds) * ra.node_count : 0);
+    ws.o_verdict = a.reserve(4 * (size_t)ncov);
+    ws.o_refits = a.reserve(4);
+    TRY(a.alloc());
+    // nothing has run yet: zero refits, and every covered object is searched through the build's tree
+    const std::vector<uint32_t> ones(ncov, 1u);
+    TRY(hipMemsetAsync(a.at<void>(0), 0, std::max<size_t>(a.need, 256), s));
+    TRY(hipMemcpyAsync(a.at<DevObj>(ws.o_objs), objs.data(), sizeof(DevObj) * ncov, hipMemcpyHostToDevice, s));
+    TRY(hipMemcpyAsync(a.at<uint32_t>(ws.o_verdict), ones.data(), 4 * (size_t)ncov, hipMemcpyHostToDevice, s));
+    TRY(hipStreamSynchronize(s));  // (the uploads' sources are this call's)
+    ws.bytes = std::max<size_t>(a.need, 256);
+    ws.ncov = ncov;
+    ws.blocks = objs.back().block_begin + (objs.back().faces + kBlock - 1) / kBlock;
+    ws.first_deep = accel::refit_first_deep(max_full);
+    ws.mem = std::move(a.mem);
+    return hipSuccess;
+}
+
+// Memory safety of the level passes whatever the faces hold (they run before the verdict is known
+// to anyone): level_node takes every range from the layout (node_range, first_child: C, full,
+// extra), make_leaf indexes faces / alpha_beta by entries of the index array — which the build
+// filled with the object's face indices and which a refit only permutes inside leaf ranges — and
+// stores to slots and node ids computed from the layout; make_inner reads two node ids computed from
+// the layout.  No face value (NaN, infinite, huge) reaches an index: such values end in boxes and
+// margins of an object whose record then says has = 0.
+hipError_t accel_refit_enqueue(const TriHot* d_hot, RayAccel& ra, hipStream_t s) {
+    const RefitWorkspace& ws = ra.refit;
+    const uint32_t ncov = ws.ncov;
+    if (!ws.ready() || !ncov) return hipSuccess;
+    unsigned char* base = ws.mem;
+    DevObj* d_objs = reinterpret_cast<DevObj*>(base + ws.o_objs);
+    DevAcc* d_acc = reinterpret_cast<DevAcc*>(base + ws.o_acc);
+    DevCount* d_cnt = reinterpret_cast<DevCount*>(base + ws.o_cnt);
+    uint32_t* d_flags = reinterpret_cast<uint32_t*>(base + ws.o_flags);
+    double* d_ab = reinterpret_cast<double*>(base + ws.o_ab);
+    accel::NodeBounds* d_bounds = reinterpret_cast<accel::NodeBounds*>(base + ws.o_bounds);
+    const uint32_t og = (ncov + kBlock - 1) / kBlock;
+    refit_reset_kernel<<<og, kBlock, 0, s>>>(d_acc, d_cnt, ncov);
+    TRY(hipGetLastError());
+    if (ws.blocks) {
+        margin_kernel<<<ws.blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, reinterpret_cast<double2*>(d_ab), d_acc, d_cnt);
+        TRY(hipGetLastError());
+        refit_check_kernel<<<ws.blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, ra.index, ra.hot, d_cnt);
+        TRY(hipGetLastError());
+    }
+    if (ra.node_count) {
+        const uint32_t first_deep = ra.refit_top_levels ? ws.first_deep : 0u;
+        for (uint32_t level = ra.max_depth; level-- > first_deep;) {
+            const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
+            for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
+                refit_level_kernel<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes,
+                                                                                             d_bounds, ra.hot, ra.index);
+                TRY(hipGetLastError());
+            }
+        }
+        if (first_deep) {
+            refit_top_levels_kernel<<<ncov, kBlock, 0, s>>>(std::min(first_deep, ra.max_depth), 0u, d_hot, d_objs, d_ab, ra.nodes, d_bounds,
+                                                            ra.hot, ra.index);
+            TRY(hipGetLastError());
+        }
+    }
+    refit_object_kernel<<<og, kBlock, 0, s>>>(d_objs, ncov, d_acc, d_cnt, ra.objs, reinterpret_cast<uint32_t*>(base + ws.o_verdict),
+                                              reinterpret_cast<uint32_t*>(base + ws.o_refits));
+    return hipGetLastError();
+}
+
+hipError_t accel_refit_status(const RayAccel& ra, hipStream_t s, uint32_t* refits, uint32_t* kept) {
+    const RefitWorkspace& ws = ra.refit;
+    *refits = *kept = 0;
+    if (!ws.ready()) return hipSuccess;
+    unsigned char* base = ws.mem;
+    std::vector<uint32_t> verdict(ws.ncov);
+    TRY(hipStreamSynchronize(s));
+    TRY(hipMemcpy(verdict.data(), base + ws.o_verdict, 4 * (size_t)ws.ncov, hipMemcpyDeviceToHost));
+    TRY(hipMemcpy(refits, base + ws.o_refits, 4, hipMemcpyDeviceToHost));
+    for (uint32_t v : verdict) *kept += v ? 1u : 0u;
     return hipSuccess;
 }
 

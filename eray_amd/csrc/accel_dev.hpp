@@ -42,5 +42,17 @@ hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObj
 // rebuilds.  Temporaries (flags, margins, per-node double bounds) are released before it returns.
 hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, AccelDevInfo* info, bool* kept);
 
+// The same refit without the host in it (eray_scene_refit_ray_accel_async).  accel_refit_workspace
+// allocates ra.refit for ra.layout, uploads the layout and waits (not during a capture);
+// accel_refit_enqueue then only launches kernels on s — the reset of the accumulators, the margin and
+// check passes, the levels (those of at most kBlock nodes in one launch per default), and
+// refit_object_kernel, which takes the verdict per covered object and writes its record: has = 0 where
+// a face changed class, so that queries scan that object until a later refit passes.  No copy, no
+// wait, no allocation: capturable.  accel_refit_status waits for s and reads the count of executed
+// refits and how many covered objects passed the last one.
+hipError_t accel_refit_workspace(RayAccel& ra, hipStream_t s);
+hipError_t accel_refit_enqueue(const TriHot* d_hot, RayAccel& ra, hipStream_t s);
+hipError_t accel_refit_status(const RayAccel& ra, hipStream_t s, uint32_t* refits, uint32_t* kept);
+
 }  // namespace gpu
 }  // namespace eray

@@ -218,5 +218,38 @@ ERAY_HD void level_node(const TreeLayout& t, uint32_t level, uint32_t j, const u
     bounds[id[0]] = nb;
 }
 
+// The refit's verdict on one covered object (accel_dev.hip refit_object_kernel, and the host's
+// comparison in accel_refit_device): the topology laid out for C culled and U unculled faces still
+// fits when the margin pass counted the same classes and the check pass found every listed
+// unculled face still unculled (status 0).  Counts and flags only: no face value is looked at, so
+// NaN, infinite or huge faces (which have no provable margin: unculled) simply change the counts.
+ERAY_HD bool refit_keeps(uint32_t culled, uint32_t unculled, uint32_t status, uint32_t C, uint32_t U) {
+    return status == 0u && culled == C && unculled == U;
+}
+
+// The object record after a refit on the stream: on a pass what the build writes (object_kernel);
+// otherwise has = 0, and the query kernels scan the object as without a hierarchy until a later
+// refit passes.  gamma: the max gamma_f of the culled faces as the margin pass reduced it.
+ERAY_HD Object refit_object(bool keeps, uint32_t C, uint32_t U, uint32_t node_base, uint32_t slot_base, double gamma) {
+    Object r{};
+    if (!keeps) return r;
+    r.has = 1;
+    r.root = C ? node_base : kNoNode;
+    r.ubegin = slot_base;
+    r.ucount = U;
+    r.gamma = up(C ? gamma : 0.0);
+    return r;
+}
+
+// Levels 0 .. kTopLevels - 1 of a tree hold at most kTopBlock nodes each: one workgroup of
+// kTopBlock lanes runs them in one launch (refit_top_levels_kernel), deepest first with a barrier
+// between levels.  The pairs level full + 1 has one lane per node of level `full`, so it fits as
+// well when full < kTopLevels.  first_deep: the shallowest level that per-level launches ran
+// (kTopLevels when some tree has a complete level kTopLevels, else kTopLevels + 1: level kTopLevels
+// is then at most the pairs level of trees with full == kTopLevels - 1).
+constexpr uint32_t kTopBlock = 256, kTopLevels = 9;
+static_assert((1u << (kTopLevels - 1)) == kTopBlock, "the last top level fills the workgroup");
+ERAY_HD uint32_t refit_first_deep(uint32_t max_full) { return max_full >= kTopLevels ? kTopLevels : kTopLevels + 1u; }
+
 }  // namespace accel
 }  // namespace eray

@@ -1546,6 +1546,22 @@ int build_accel_device(eray_ctx* ctx, uint32_t min_faces, std::chrono::steady_cl
     if (info) *info = out;
     return ERAY_OK;
 }
+
+// Can a refit keep the topology?  The last build was the device's and covered these objects, at
+// these places, with these face counts, and no object was added and the scene not reset since
+// (objs has a record per object of the build's scene: the arrays fit that scene only).
+bool same_layout(const eray_ctx* ctx) {
+    const RayAccel& ra = ctx->ray_accel;
+    bool same = ra.builder == RayAccel::kDevice && !ra.scene_changed && ra.objs.cap == ctx->objects.size();
+    if (same) {
+        const std::vector<AccelDevObject> covered = covered_objects(ctx, ra.min_faces);
+        same = covered.size() == ra.layout.size();
+        for (size_t i = 0; same && i < covered.size(); ++i)
+            same = covered[i].index == ra.layout[i].index && covered[i].hot_begin == ra.layout[i].hot_begin &&
+                   covered[i].faces == ra.layout[i].faces;
+    }
+    return same;
+}
 }  // namespace
 
 extern "C" {
@@ -1571,17 +1587,7 @@ int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
     if (int st = sync_scene(ctx)) return st;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the arrays)
     eray_ray_accel_refit_info out{};
-    // the last build was the device's and covered these objects, with these face counts?
-    // ... and no object was added and the scene not reset since (objs has a record per object of the
-    // build's scene: the arrays fit that scene only)
-    bool same = ra.builder == RayAccel::kDevice && !ra.scene_changed && ra.objs.cap == ctx->objects.size();
-    if (same) {
-        const std::vector<AccelDevObject> covered = covered_objects(ctx, ra.min_faces);
-        same = covered.size() == ra.layout.size();
-        for (size_t i = 0; same && i < covered.size(); ++i)
-            same = covered[i].index == ra.layout[i].index && covered[i].hot_begin == ra.layout[i].hot_begin &&
-                   covered[i].faces == ra.layout[i].faces;
-    }
+    const bool same = same_layout(ctx);
     bool kept = false;
     if (same) {
         AccelDevInfo dev;
@@ -1604,6 +1610,53 @@ int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
         out.rebuilt = 1;
     }
     if (info) *info = out;
+    return ERAY_OK;
+}
+
+// The kept-topology refit enqueued on the context's stream (accel_dev.hip accel_refit_enqueue): the
+// device takes the verdict per covered object and writes it into the object's `has` word, so the
+// host neither waits nor reads; with its workspace in place the call only launches kernels and can
+// be captured.  It never rebuilds: where eray_scene_refit_ray_accel would, it refuses.
+int eray_scene_refit_ray_accel_async(eray_ctx* ctx) {
+    static const char* const fn = "eray_scene_refit_ray_accel_async";
+    if (!ctx) return set_error(nullptr, ERAY_E_INVALID_ARGUMENT, "null context");
+    RayAccel& ra = ctx->ray_accel;
+    if (ra.builder == RayAccel::kNone)
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: the scene has no ray-query hierarchy to refit", fn);
+    if (ra.builder != RayAccel::kDevice)
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: the hierarchy was built on the host (only a device build is refitted)", fn);
+    if (!same_layout(ctx))
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
+                         "%s: the scene's objects are not those of the build (eray_scene_refit_ray_accel rebuilds)", fn);
+    // first of all HIP calls, so that a refusal leaves a capture as it was (the null stream never
+    // captures and is not asked: order_after_side_streams)
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (ctx->stream) HIP_TRY(ctx, hipStreamIsCapturing(ctx->stream, &capturing));
+    if (!ra.refit.ready()) {
+        if (capturing != hipStreamCaptureStatusNone)
+            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: no workspace yet: call once outside a capture first", fn);
+        if (int st = use_device(ctx)) return st;
+        HIP_TRY(ctx, accel_refit_workspace(ra, ctx->stream));
+    }
+    if (int st = use_device(ctx)) return st;
+    HIP_TRY(ctx, accel_refit_enqueue(ctx->d_hot, ra, ctx->stream));
+    ra.valid = true;  // (per object the device's `has` word carries the truth)
+    return ERAY_OK;
+}
+
+int eray_scene_ray_accel_refit_status(eray_ctx* ctx, eray_ray_accel_refit_status* out) {
+    if (int st = use_device(ctx)) return st;
+    if (!out) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_scene_ray_accel_refit_status: out is null");
+    const RayAccel& ra = ctx->ray_accel;
+    if (!ra.refit.ready())
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
+                         "eray_scene_ray_accel_refit_status: no refit workspace (eray_scene_refit_ray_accel_async makes it)");
+    eray_ray_accel_refit_status s{};
+    HIP_TRY(ctx, accel_refit_status(ra, ctx->stream, &s.refits, &s.kept));
+    s.covered = ra.refit.ncov;
+    s.fell_back = s.covered - s.kept;
+    s.workspace_bytes = ra.refit.bytes;
+    *out = s;
     return ERAY_OK;
 }
 
@@ -2605,6 +2658,34 @@ extern "C" int eray_debug_ray_accel_check(eray_ctx* ctx, char* msg, uint32_t cap
     const char* bad = eray::accel::check(faces.data(), sizes.data(), nobj, ra.min_faces, objs.data(), nodes.data(), nodes.size(),
                                          hot.data(), index.data(), index.size());
     return bad ? say(ERAY_E_BUILD, bad) : ERAY_OK;
+}
+// One of the hierarchy's device arrays as it stands (valid or not, once the stream is idle), so
+// that tests compare whole arrays: which = 0 the Object records, 1 the nodes, 2 the leaf-ordered
+// face records, 3 the index array.  *bytes: its size; copied when out holds that much.
+extern "C" int eray_debug_ray_accel_arrays(eray_ctx* ctx, uint32_t which, void* out, size_t cap, size_t* bytes) {
+    if (int st = use_device(ctx)) return st;
+    const RayAccel& ra = ctx->ray_accel;
+    if (!bytes || which > 3) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_ray_accel_arrays: bad argument");
+    if (ra.builder == RayAccel::kNone)
+        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_ray_accel_arrays: the scene has no ray-query hierarchy");
+    const void* src[4] = {(const eray::accel::Object*)ra.objs, (const eray::accel::Node*)ra.nodes, (const eray::accel::Hot*)ra.hot,
+                          (const uint32_t*)ra.index};
+    const size_t size[4] = {sizeof(eray::accel::Object) * ra.objs.cap, sizeof(eray::accel::Node) * ra.node_count,
+                            sizeof(eray::accel::Hot) * ra.slot_count, 4 * ra.slot_count};
+    *bytes = size[which];
+    if (!out) return ERAY_OK;
+    if (cap < size[which]) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_ray_accel_arrays: out holds %zu of %zu bytes", cap, size[which]);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (size[which]) HIP_TRY(ctx, hipMemcpy(out, src[which], size[which], hipMemcpyDeviceToHost));
+    return ERAY_OK;
+}
+// Diagnostics: whether eray_scene_refit_ray_accel_async runs the levels of at most 256 nodes in one
+// launch (the default) or every level in a launch of its own; the bytes are the same.  Read when the
+// call enqueues: a captured graph keeps the form it was captured with.
+extern "C" int eray_debug_set_refit_top_levels(eray_ctx* ctx, int on) {
+    if (!ctx) return ERAY_E_INVALID_ARGUMENT;
+    ctx->ray_accel.refit_top_levels = on != 0;
+    return ERAY_OK;
 }
 
 extern "C" uint64_t eray_debug_bin_capacity(const eray_ctx* ctx) { return ctx ? (uint64_t)ctx->bins.cap : 0u; }

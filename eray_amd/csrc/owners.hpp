@@ -120,6 +120,23 @@ struct AccelDevLayout {
     uint32_t node_base, full, extra, pad;  // (accel_layout.hpp TreeLayout)
 };
 
+// What eray_scene_refit_ray_accel_async works in (accel_dev.hip accel_refit_workspace): one device
+// allocation that lives from the first eligible call outside a capture until the next build or
+// drop — the uploaded layout, the accumulators and counters, per face the flag and (alpha, beta),
+// per node the double bounds, per covered object the verdict, and the count of refits executed.
+struct RefitWorkspace {
+    DeviceBuf<unsigned char> mem;
+    size_t o_objs = 0, o_acc = 0, o_cnt = 0, o_flags = 0, o_ab = 0, o_bounds = 0, o_verdict = 0, o_refits = 0;
+    size_t bytes = 0;
+    uint32_t ncov = 0, blocks = 0, first_deep = 0;
+    bool ready() const { return (unsigned char*)mem != nullptr; }
+    void release() {
+        (void)mem.release();
+        bytes = 0;
+        ncov = blocks = first_deep = 0;
+    }
+};
+
 struct RayAccel {
     DeviceBuf<accel::Object> objs;
     DeviceBuf<accel::Node> nodes;
@@ -138,7 +155,12 @@ struct RayAccel {
     // eray_scene_add_object or eray_scene_reset happened since the build: `objs` holds a record per
     // object of the scene as it was, so the arrays fit the old scene only — a refit rebuilds
     bool scene_changed = false;
+    // the async refit's workspace (fits `layout`: released with it) and whether it runs the upper
+    // levels in one launch (a setting of eray_debug_set_refit_top_levels: it outlives drop())
+    RefitWorkspace refit;
+    bool refit_top_levels = true;
     void drop() {
+        refit.release();
         valid = false;
         min_faces = 0;
         node_count = slot_count = 0;

@@ -494,7 +494,10 @@ int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ra
  * was refitted or built before the replay still describe the geometry of the last direct call and
  * would answer for it silently.  After replays, make one direct eray_scene_update_object call with
  * the current arrays (and eray_scene_refit_ray_accel, if a hierarchy is in use) before rendering or
- * querying through a hierarchy.
+ * querying through a hierarchy.  A graph that holds the update AND eray_scene_refit_ray_accel_async
+ * (below) after it keeps the hierarchy current on every replay: the queries of the same graph and
+ * later direct ray queries search a tree that describes the replayed geometry.  The caveat for
+ * eray_render stays.
  *
  * Errors (ERAY_E_INVALID_ARGUMENT, nothing changed): update NULL, an index that is not an object of
  * the scene, a triangle_count that is not the object's (eray_scene_object_triangle_count returns
@@ -546,6 +549,54 @@ typedef struct eray_ray_accel_refit_info {  /*                                  
     uint32_t rebuilt;               /* offset 52: 1: the call fell back to a full device build */
 } eray_ray_accel_refit_info;
 int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info /* may be NULL */);
+
+/* The kept-topology refit above, enqueued on the context's stream: the call returns at once, and
+ * once its workspace exists it makes no host read-back, no synchronisation, no allocation and no
+ * copy from host memory, so it can be captured into a HIP graph after an
+ * eray_scene_update_object(ERAY_UPDATE_DEVICE) and before the queries that follow.  The comparison
+ * the synchronous call makes on the host — per covered object, the counted culled and unculled
+ * faces are the build's and every listed unculled face still is one — is made by a kernel, which
+ * writes the object's record: on a pass what a build writes; otherwise a record that says "no
+ * hierarchy", and the queries scan THAT OBJECT face by face, as they do for an object below
+ * min_faces: the same first face, the same u, v, t bits, only slower.  The level passes run either
+ * way; they index by the build's layout alone and are memory-safe for any face values (NaN,
+ * infinite, huge).  A later async refit of the same object passes again as soon as its faces'
+ * classes are the build's again — the index array is only ever permuted inside leaf ranges and the
+ * unculled slots are not rewritten on a failure — so no rebuild is needed for that.  The levels of
+ * at most 256 nodes of each tree run in one launch, the deeper ones in a launch each.
+ *
+ * ELIGIBILITY is that of a kept topology above: the last build was
+ * eray_scene_build_ray_accel_device (or a rebuild by eray_scene_refit_ray_accel), no
+ * eray_scene_add_object and no eray_scene_reset happened since, and the covered objects, their
+ * places and face counts are the build's.  Otherwise ERAY_E_INVALID_ARGUMENT, nothing is enqueued
+ * and the hierarchy's validity is unchanged: this call never rebuilds.  On success the hierarchy
+ * counts as valid from the host's side at once; per object the device's record carries the truth.
+ *
+ * WORKSPACE.  The call works in one persistent device allocation (the uploaded layout, the
+ * accumulators and counters, 20 B per covered face, 64 B per node, a verdict per covered object
+ * and a counter), made — with a wait — by the first eligible call while the stream is not
+ * capturing, and released by eray_scene_drop_ray_accel and by every build (a rebuild by
+ * eray_scene_refit_ray_accel included); a graph that captured the call must not be replayed after
+ * that.  During a capture without a workspace the call returns ERAY_E_INVALID_ARGUMENT ("call once
+ * outside a capture first") and the capture stays usable.  Present in builds that define
+ * ERAY_HAS_RAY_ACCEL_REFIT_ASYNC. */
+#define ERAY_HAS_RAY_ACCEL_REFIT_ASYNC 1
+int eray_scene_refit_ray_accel_async(eray_ctx* ctx);
+/* What the async refits did, read after waiting for the context's stream (synchronous).  An object
+ * counted in fell_back is answered for correctly, by scanning; the diagnostics' hierarchy check
+ * (eray_hip_debug.h) rejects such a state (a covered object without a record), so this call is how
+ * to see it.  Before the first refit has run: refits = 0, kept = covered.  Errors:
+ * ERAY_E_INVALID_ARGUMENT when out is NULL or no workspace exists (none made yet, or released by a
+ * build or a drop). */
+typedef struct eray_ray_accel_refit_status {   /*                                        32 B */
+    uint32_t refits;          /* offset 0:  async refits the device has executed since the workspace was made */
+    uint32_t covered;         /* offset 4:  objects with a hierarchy                            */
+    uint32_t kept;            /* offset 8:  covered objects searched through the hierarchy after the last one */
+    uint32_t fell_back;       /* offset 12: covered objects scanned per ray until a later refit passes */
+    uint64_t workspace_bytes; /* offset 16: the workspace's device allocation                   */
+    uint64_t reserved;        /* offset 24: 0                                                   */
+} eray_ray_accel_refit_status;
+int eray_scene_ray_accel_refit_status(eray_ctx* ctx, eray_ray_accel_refit_status* out);
 
 /* Engine::reaches_light (engine.rs:218-228) for shadow rays the caller supplies: "does this point
  * see that point" for light baking, visibility probes and a caller's own shading.  Per ray i:

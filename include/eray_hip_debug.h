@@ -89,8 +89,19 @@ int eray_debug_gather_layout(const int32_t* rects, uint32_t n, uint32_t height, 
  * and checked on the host (eray_amd/csrc/accel_check.hpp: permutation and byte copies, the
  * unculled list, leaf order, min_index / right_min, boxes, alpha / beta / gamma, reachability,
  * depth).  ERAY_OK, or an error with the first violated invariant in msg (at most cap bytes,
- * may be null) and in eray_last_error. */
+ * may be null) and in eray_last_error.  A state in which eray_scene_refit_ray_accel_async left a
+ * covered object without a record (it fell back to the scan) is rejected as well, although the
+ * queries answer for it correctly: eray_scene_ray_accel_refit_status tells the two apart. */
 int eray_debug_ray_accel_check(eray_ctx* ctx, char* msg, uint32_t cap);
+/* One of the hierarchy's four device arrays as it stands, valid or not, copied to the host after a
+ * wait for the stream: which = 0 the per-object records (32 B per object of the scene), 1 the nodes
+ * (48 B each), 2 the leaf-ordered face records (48 B per slot), 3 the index array (4 B per slot).
+ * *bytes receives the array's size; out (may be NULL: the size alone) must hold it (cap). */
+int eray_debug_ray_accel_arrays(eray_ctx* ctx, uint32_t which, void* out, size_t cap, size_t* bytes);
+/* Whether eray_scene_refit_ray_accel_async runs each tree's levels of at most 256 nodes in one
+ * launch (on != 0, the default) or every level in a launch of its own; the bytes written are the
+ * same.  Read when the call enqueues, so a captured graph keeps the form it was captured with. */
+int eray_debug_set_refit_top_levels(eray_ctx* ctx, int on);
 
 #ifdef __cplusplus
 }
