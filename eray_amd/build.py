@@ -97,20 +97,19 @@ BIN_DIR = os.path.join(PKG, "bin")
 ROCM_LIB = "/opt/rocm/lib"
 
 
-# tests/cpp/accel_walk_main.cpp: f32 as the kernels compute it (no fused multiply-add)
+# the CPU programs of the ray-query hierarchy (tests/cpp/accel_*_main.cpp over tests/cpp/accel_emul.hpp): f32 as the
+# kernels compute it (no fused multiply-add); what all but accel_walk_main compile with, and what they depend on
+# (with every header that tests/cpp/ holds: the programs' shared part)
 ACCEL_WALK_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-pthread"]
-
-
-# tests/cpp/accel_dev_main.cpp: the same flags; what it compiles with and depends on
 ACCEL_DEV_SOURCES = [os.path.join(CSRC, "accel_build.cpp"), os.path.join(CSRC, "accel_check.cpp")]
 ACCEL_DEV_HEADERS = ["accel_build.hpp", "accel_walk.hpp", "accel_margin.hpp", "accel_layout.hpp", "accel_check.hpp"]
-
-
-# tests/cpp/accel_refit_main.cpp (the same flags and sources) and tests/cpp/update_args_main.cpp (headers only)
-REFIT_MAIN = os.path.join(ROOT, "tests", "cpp", "accel_refit_main.cpp")
-UPDATE_ARGS_MAIN = os.path.join(ROOT, "tests", "cpp", "update_args_main.cpp")
-# tests/cpp/accel_refit_async_main.cpp: the refit on the stream, the same flags and sources
-REFIT_ASYNC_MAIN = os.path.join(ROOT, "tests", "cpp", "accel_refit_async_main.cpp")
+TESTS_CPP = os.path.join(ROOT, "tests", "cpp")
+WALK_MAIN = os.path.join(TESTS_CPP, "accel_walk_main.cpp")
+DEV_MAIN = os.path.join(TESTS_CPP, "accel_dev_main.cpp")
+REFIT_MAIN = os.path.join(TESTS_CPP, "accel_refit_main.cpp")
+REFIT_ASYNC_MAIN = os.path.join(TESTS_CPP, "accel_refit_async_main.cpp")
+# tests/cpp/update_args_main.cpp (headers only)
+UPDATE_ARGS_MAIN = os.path.join(TESTS_CPP, "update_args_main.cpp")
 UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "include", "eray_hip.h")]
 
 
@@ -160,30 +159,19 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
         if force or not _newer(exe, [src, HOST_LIB] + headers):
             run([cxx, *flags, src, "-o", exe, "-L" + LIB_DIR, "-leray_host", *link])
         outs.append(exe)
-    # the ray-query hierarchy on the CPU: the builder and the shared walk, no GPU library
-    walk_src = [os.path.join(ROOT, "tests", "cpp", "accel_walk_main.cpp"), os.path.join(CSRC, "accel_build.cpp")]
-    exe = os.path.join(BIN_DIR, "accel_walk_main")
-    if force or not _newer(exe, walk_src + [os.path.join(CSRC, h) for h in ("accel_build.hpp", "accel_walk.hpp",
-                                                                            "accel_margin.hpp")]):
-        run([cxx, *ACCEL_WALK_FLAGS, *walk_src, "-o", exe])
-    outs.append(exe)
-    # the device-side builder emulated on the CPU with the headers its kernels share, and the checker
-    dev_src = [os.path.join(ROOT, "tests", "cpp", "accel_dev_main.cpp"), *ACCEL_DEV_SOURCES]
-    exe = os.path.join(BIN_DIR, "accel_dev_main")
-    if force or not _newer(exe, dev_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
-        run([cxx, *ACCEL_WALK_FLAGS, *dev_src, "-o", exe])
-    outs.append(exe)
-    # the refit of a device-built hierarchy emulated the same way, and the update's argument checks
-    refit_src = [REFIT_MAIN, *ACCEL_DEV_SOURCES]
-    exe = os.path.join(BIN_DIR, "accel_refit_main")
-    if force or not _newer(exe, refit_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
-        run([cxx, *ACCEL_WALK_FLAGS, *refit_src, "-o", exe])
-    outs.append(exe)
-    async_src = [REFIT_ASYNC_MAIN, *ACCEL_DEV_SOURCES]
-    exe = os.path.join(BIN_DIR, "accel_refit_async_main")
-    if force or not _newer(exe, async_src + [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]):
-        run([cxx, *ACCEL_WALK_FLAGS, *async_src, "-o", exe])
-    outs.append(exe)
+    # the ray-query hierarchy on the CPU (what the programs share is tests/cpp/accel_emul.hpp): the builder and
+    # the shared walk; the device-side builder, its refit and the refit on the stream emulated with the headers
+    # their kernels share, and the checker.  No GPU library.  (The update's argument checks follow.)
+    accel_deps = [os.path.join(TESTS_CPP, f) for f in sorted(os.listdir(TESTS_CPP)) if f.endswith(".hpp")]
+    accel_deps += [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]
+    for name, main_src, more in (("accel_walk_main", WALK_MAIN, [os.path.join(CSRC, "accel_build.cpp")]),
+                                 ("accel_dev_main", DEV_MAIN, ACCEL_DEV_SOURCES),
+                                 ("accel_refit_main", REFIT_MAIN, ACCEL_DEV_SOURCES),
+                                 ("accel_refit_async_main", REFIT_ASYNC_MAIN, ACCEL_DEV_SOURCES)):
+        exe = os.path.join(BIN_DIR, name)
+        if force or not _newer(exe, [main_src, *more, *accel_deps]):
+            run([cxx, *ACCEL_WALK_FLAGS, main_src, *more, "-o", exe])
+        outs.append(exe)
     exe = os.path.join(BIN_DIR, "update_args_main")
     if force or not _newer(exe, [UPDATE_ARGS_MAIN, *UPDATE_ARGS_HEADERS]):
         run([cxx, "-std=c++17", "-O2", "-Wall", UPDATE_ARGS_MAIN, "-o", exe])

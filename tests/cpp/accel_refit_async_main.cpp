@@ -1,15 +1,16 @@
 // accel_refit_async_main.cpp — the refit that runs on the stream (accel_dev.hip accel_refit_enqueue)
-// emulated on the CPU with the headers its kernels share (accel_margin.hpp, accel_layout.hpp), the
-// checker (accel_check.cpp) and the walk the kernel runs (accel_walk.hpp).  No GPU, no HIP.  Compile
-// with -ffp-contract=off.
+// emulated on the CPU, kernel for kernel, with the headers its kernels share (accel_margin.hpp,
+// accel_layout.hpp), the checker (accel_check.cpp) and the walk the kernel runs (accel_walk.hpp).
+// The device build, the synchronous refit it is compared with, the ray sets and the meshes are
+// accel_emul.hpp's; this program adds the scene, the persistent workspace, refit_async and the
+// dispatch of queries by the records' `has`.  No GPU, no HIP.  Compile with -ffp-contract=off.
 //
 //   accel_refit_async_main <sphere2000.bin> [rays]
 //
-// A scene of two covered objects is built on meshes A (emulate_device_build, as
-// tests/cpp/accel_refit_main.cpp; its generators and ray sets, copied) and refitted through ONE
-// workspace that is never cleared except by the documented resets (the accumulators and counters):
-// the margin pass, the check of the unculled lists, the level passes whatever the verdict, the
-// verdict (accel::refit_keeps) and the object record (accel::refit_object).
+// A scene of two covered objects is built on meshes A (emulate_device_build) and refitted through
+// ONE workspace that is never cleared except by the documented resets (the accumulators and
+// counters): the margin pass, the check of the unculled lists, the level passes whatever the
+// verdict, the verdict (accel::refit_keeps) and the object record (accel::refit_object).
 //   reuse=...         A -> B -> C through the reused workspace: same=1 when nodes, slots, indices and
 //                     records equal a synchronous-style refit from A straight to C (emulate_refit),
 //                     check=1 when accel::check accepts the scene, top=1 when the order of
@@ -19,306 +20,12 @@
 //                     that differ from the linear scan, healed=1 when the last refit's bytes are
 //                     those of a refit that never saw the bad mesh
 // tests/test_accel_refit_async_host.py asserts on the figures.
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../eray_amd/csrc/accel_build.hpp"
-#include "../../eray_amd/csrc/accel_check.hpp"
-#include "../../eray_amd/csrc/accel_layout.hpp"
+#include "accel_emul.hpp"
 
 using namespace eray::accel;
+using namespace accel_emul;
 
 namespace {
-
-struct F3 {
-    float x, y, z;
-};
-F3 sub(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-F3 cross(F3 s, F3 o) { return {s.y * o.z - s.z * o.y, s.z * o.x - s.x * o.z, s.x * o.y - s.y * o.x}; }
-float dot0(F3 a, F3 b) {
-    float acc = 0.0f;
-    acc = acc + a.x * b.x;
-    acc = acc + a.y * b.y;
-    acc = acc + a.z * b.z;
-    return acc;
-}
-
-// The record of face (a, b, c): e1 = b - a, e2 = c - a, n = e1 x e2 (primitives.rs:44-46).
-Hot make_hot(const float* p) {
-    const F3 a{p[0], p[1], p[2]}, b{p[3], p[4], p[5]}, c{p[6], p[7], p[8]};
-    const F3 e1 = sub(b, a), e2 = sub(c, a), n = cross(e1, e2);
-    return Hot{{e1.x, e1.y, e1.z, e2.x, e2.y, e2.z, n.x, n.y, n.z, a.x, a.y, a.z}};
-}
-
-// Triangle::intersects with the precomputed record (hit.hpp exact_test), plain f32.
-bool exact_test(const Hot& r, F3 o, F3 d) {
-    const F3 e1{r.q[0], r.q[1], r.q[2]}, e2{r.q[3], r.q[4], r.q[5]}, n{r.q[6], r.q[7], r.q[8]}, a{r.q[9], r.q[10], r.q[11]};
-    if (dot0(n, d) > 0.0f) return false;
-    const float det = -dot0(d, n);
-    if (!(det >= 1e-6f)) return false;
-    const float invdet = 1.0f / det;
-    const F3 ao = sub(o, a), dao = cross(ao, d);
-    const float u = dot0(e2, dao) * invdet, v = -dot0(e1, dao) * invdet, t = dot0(ao, n) * invdet;
-    return t >= 0.0f && u >= 0.0f && v >= 0.0f && (u + v) <= 1.0f;
-}
-
-struct Ray {
-    float o[3], d[3];
-    bool in_range;  // finite, |d|2 in [1e-3, 1e3]: must not be a fallback ray
-};
-
-struct HostStack {
-    uint32_t v[kStackDepth];
-    uint32_t n = 0, high = 0;
-    void push(uint32_t x) {
-        if (n >= kStackDepth) {
-            std::fprintf(stderr, "stack overflow\n");
-            std::abort();
-        }
-        v[n++] = x;
-        high = n > high ? n : high;
-    }
-    uint32_t pop() { return v[--n]; }
-    bool empty() const { return n == 0; }
-};
-
-std::mt19937_64 g_rng(12345);
-double uni(double lo, double hi) { return std::uniform_real_distribution<double>(lo, hi)(g_rng); }
-double gauss() { return std::normal_distribution<double>(0.0, 1.0)(g_rng); }
-
-Ray mk(const double* o, const double* d) {
-    Ray r;
-    for (int k = 0; k < 3; ++k) {
-        r.o[k] = (float)o[k];
-        r.d[k] = (float)d[k];
-    }
-    bool fin = true;
-    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(r.o[k]) && std::isfinite(r.d[k]);
-    const double len = std::sqrt((double)r.d[0] * r.d[0] + (double)r.d[1] * r.d[1] + (double)r.d[2] * r.d[2]);
-    r.in_range = fin && len >= 1e-3 && len <= 1e3;
-    return r;
-}
-
-// n rays from the radius-3 sphere (times `far`) toward targets uniform in [-1, 1]^3, dir scaled
-void sphere_rays(std::vector<Ray>& out, size_t n, double far, double scale) {
-    for (size_t i = 0; i < n; ++i) {
-        double v[3] = {gauss(), gauss(), gauss()};
-        const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        double o[3], d[3];
-        for (int k = 0; k < 3; ++k) {
-            o[k] = 3.0 * far * v[k] / l;
-            d[k] = (uni(-1, 1) - o[k]) * scale;
-        }
-        out.push_back(mk(o, d));
-    }
-}
-
-// rays built from the mesh's own faces: grazing, along edges, through vertices, axis-parallel,
-// starts on box planes, scaled directions, far starts, non-finite components
-void adversarial_rays(std::vector<Ray>& out, const std::vector<float>& pos, size_t n) {
-    const size_t T = pos.size() / 9;
-    const double angles[5] = {1e-7, 1e-6, 1e-5, 1e-4, 1e-3};
-    const double scales[3] = {1.0, 1e-3, 1e3};
-    for (size_t i = 0; i < n; ++i) {
-        const float* p = &pos[9 * (g_rng() % T)];
-        double a[3], e1[3], e2[3], nn[3];
-        for (int k = 0; k < 3; ++k) {
-            a[k] = p[k];
-            e1[k] = (double)p[3 + k] - p[k];
-            e2[k] = (double)p[6 + k] - p[k];
-        }
-        nn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-        nn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-        nn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-        const double nl = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
-        const double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-        if (!(nl > 0.0) || !(l1 > 0.0)) continue;
-        double bu = uni(0, 1), bv = uni(0, 1);
-        if (bu + bv > 1) {
-            bu = 1 - bu;
-            bv = 1 - bv;
-        }
-        double P[3], o[3], d[3];
-        for (int k = 0; k < 3; ++k) P[k] = a[k] + bu * e1[k] + bv * e2[k];
-        const int kind = (int)(i % 8);
-        const double sc = scales[(i / 8) % 3];
-        if (kind <= 2) {  // within `ang` of the face's plane, through P, from the front
-            const double ang = angles[(i / 24) % 5] * (kind == 2 ? -1.0 : 1.0), mix = uni(0, 1);
-            double t[3];
-            for (int k = 0; k < 3; ++k) t[k] = mix * e1[k] / l1 + (1 - mix) * (e2[k] - e1[k]);
-            const double tl = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-            for (int k = 0; k < 3; ++k) d[k] = (std::cos(ang) * t[k] / tl - std::sin(ang) * nn[k] / nl);
-            const double back = uni(0.5, 3.0);
-            for (int k = 0; k < 3; ++k) o[k] = P[k] - back * d[k], d[k] *= sc;
-        } else if (kind == 3) {  // along an edge
-            const double back = uni(0.5, 3.0);
-            for (int k = 0; k < 3; ++k) d[k] = e1[k] / l1, o[k] = a[k] - back * d[k], d[k] *= sc;
-        } else if (kind == 4) {  // through a vertex
-            double v[3] = {gauss(), gauss(), gauss()};
-            const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            for (int k = 0; k < 3; ++k) o[k] = 3.0 * v[k] / l, d[k] = (a[k] + e1[k] - o[k]) * sc;
-        } else if (kind == 5) {  // one or two zero direction components, through P
-            const int ax = (int)(g_rng() % 3), two = (int)(g_rng() % 2);
-            for (int k = 0; k < 3; ++k) d[k] = (k == ax || (two && k == (ax + 1) % 3)) ? 0.0 : (g_rng() % 2 ? 1.0 : -1.0);
-            for (int k = 0; k < 3; ++k) o[k] = P[k] - 2.5 * d[k], d[k] *= sc;
-        } else if (kind == 6) {  // a zero component with the start on a vertex's coordinate plane
-            const int ax = (int)(g_rng() % 3);
-            for (int k = 0; k < 3; ++k) d[k] = k == ax ? 0.0 : uni(-1, 1);
-            for (int k = 0; k < 3; ++k) o[k] = k == ax ? a[k] : P[k] - 3.0 * d[k];
-            for (int k = 0; k < 3; ++k) d[k] *= sc;
-        } else {  // a start at distance 1e3 toward P
-            double v[3] = {gauss(), gauss(), gauss()};
-            const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            for (int k = 0; k < 3; ++k) o[k] = 1e3 * v[k] / l, d[k] = (P[k] - o[k]) / 1e3 * sc;
-        }
-        out.push_back(mk(o, d));
-    }
-    const double bad[4] = {NAN, INFINITY, -INFINITY, 0.0};
-    for (int i = 0; i < 64; ++i) {  // non-finite components and the zero direction
-        double o[3] = {uni(-3, 3), uni(-3, 3), 3.0}, d[3] = {uni(-1, 1), uni(-1, 1), -1.0};
-        if (i < 48) (i & 1 ? o : d)[(i >> 1) % 3] = bad[(i >> 3) % 3];
-        else d[0] = d[1] = d[2] = 0.0;
-        out.push_back(mk(o, d));
-    }
-}
-
-int scan(const std::vector<Hot>& hot, F3 o, F3 d) {
-    for (size_t f = 0; f < hot.size(); ++f)
-        if (exact_test(hot[f], o, d)) return (int)f;
-    return -1;
-}
-
-// The device build of one object (accel_dev.hip), step for step on the host.
-Built emulate_device_build(const std::vector<Hot>& faces, uint32_t node_base, uint32_t slot_base) {
-    const uint32_t T = (uint32_t)faces.size();
-    Built out;
-    std::memset(&out.obj, 0, sizeof out.obj);
-    // margin pass: flags, (alpha, beta), centroid bounds and max gamma of the culled faces
-    std::vector<double> ab(2 * (size_t)T);
-    std::vector<char> unculled(T);
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, gamma = 0.0;
-    for (uint32_t f = 0; f < T; ++f) {
-        const FaceMargin m = face_margin_of(faces[f]);
-        unculled[f] = !m.culled;
-        ab[2 * (size_t)f] = m.alpha;
-        ab[2 * (size_t)f + 1] = m.beta;
-        if (!m.culled) continue;
-        double c[3];
-        centroid_of(faces[f], c);
-        for (int j = 0; j < 3; ++j) {
-            lo[j] = std::fmin(lo[j], c[j]);
-            hi[j] = std::fmax(hi[j], c[j]);
-        }
-        gamma = std::fmax(gamma, m.gamma);
-    }
-    // key pass: unculled faces to the head in ascending index, (key, index) of the others
-    out.hot.resize(T);
-    out.index.resize(T);
-    std::vector<uint64_t> keys;
-    std::vector<uint32_t> ids;
-    uint32_t U = 0;
-    for (uint32_t f = 0; f < T; ++f) {
-        if (unculled[f]) {
-            out.hot[U] = faces[f];
-            out.index[U++] = f;
-            continue;
-        }
-        double c[3];
-        centroid_of(faces[f], c);
-        keys.push_back(morton_key(c, lo, hi));
-        ids.push_back(f);
-    }
-    const uint32_t C = T - U;
-    std::vector<uint32_t> order(C);
-    for (uint32_t p = 0; p < C; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return keys[x] < keys[y]; });
-    std::vector<uint32_t> sorted(C);
-    for (uint32_t p = 0; p < C; ++p) sorted[p] = ids[order[p]] + slot_base;  // (the kernels' g = gbegin + index)
-    // levels, deepest first
-    const TreeLayout t = tree_layout(C);
-    std::vector<Node> nodes((size_t)node_base + t.nodes);  // (global ids, as on the device)
-    std::vector<NodeBounds> bounds(nodes.size());
-    std::vector<Hot> hot((size_t)slot_base + T);
-    std::vector<uint32_t> index((size_t)slot_base + T);
-    for (uint32_t level = t.depth; level-- > 0;)
-        for (uint32_t j = 0; j < (1u << level); ++j)
-            level_node(t, level, j, sorted.data(), slot_base, faces.data(), ab.data(), node_base, slot_base + U, nodes.data(),
-                       bounds.data(), hot.data(), index.data());
-    for (uint32_t s = U; s < T; ++s) {
-        out.hot[s] = hot[slot_base + s];
-        out.index[s] = index[slot_base + s];
-    }
-    out.nodes.assign(nodes.begin() + node_base, nodes.end());
-    out.unculled = U;
-    out.depth = t.depth;
-    out.obj.has = 1;
-    out.obj.root = C ? node_base : kNoNode;
-    out.obj.ubegin = slot_base;
-    out.obj.ucount = U;
-    out.obj.gamma = up(C ? gamma : 0.0);
-    return out;
-}
-
-// The synchronous refit of one object (accel_refit_device, as tests/cpp/accel_refit_main.cpp emulates
-// it): the reference the refit on the stream must equal byte for byte.  false: a class change.
-bool emulate_refit(const std::vector<Hot>& faces, const Built& built, uint32_t node_base, uint32_t slot_base, Built* out) {
-    const uint32_t T = (uint32_t)faces.size(), U = built.unculled, C = T - U;
-    std::vector<double> ab(2 * (size_t)T);
-    std::vector<char> unculled(T);
-    double gamma = 0.0;
-    uint32_t nc = 0, nu = 0;
-    for (uint32_t f = 0; f < T; ++f) {
-        const FaceMargin m = face_margin_of(faces[f]);
-        unculled[f] = !m.culled;
-        ab[2 * (size_t)f] = m.alpha;
-        ab[2 * (size_t)f + 1] = m.beta;
-        (m.culled ? nc : nu) += 1;
-        if (m.culled) gamma = std::fmax(gamma, m.gamma);
-    }
-    std::vector<Hot> hot((size_t)slot_base + T);
-    std::vector<uint32_t> index((size_t)slot_base + T);
-    std::copy(built.hot.begin(), built.hot.end(), hot.begin() + slot_base);
-    std::copy(built.index.begin(), built.index.end(), index.begin() + slot_base);
-    bool status = false;
-    for (uint32_t k = 0; k < U; ++k) {
-        const uint32_t f = index[slot_base + k];
-        if (f < T && unculled[f]) hot[slot_base + k] = faces[f];
-        else status = true;
-    }
-    if (status || nc != C || nu != U) return false;
-    const TreeLayout t = tree_layout(C);
-    std::vector<Node> nodes((size_t)node_base + t.nodes);
-    std::vector<NodeBounds> bounds(nodes.size());
-    for (uint32_t level = t.depth; level-- > 0;)
-        for (uint32_t j = 0; j < (1u << level); ++j)
-            level_node(t, level, j, index.data() + slot_base + U, 0u, faces.data(), ab.data(), node_base, slot_base + U, nodes.data(),
-                       bounds.data(), hot.data(), index.data());
-    out->hot.assign(hot.begin() + slot_base, hot.end());
-    out->index.assign(index.begin() + slot_base, index.end());
-    out->nodes.assign(nodes.begin() + node_base, nodes.end());
-    out->unculled = U;
-    out->depth = t.depth;
-    std::memset(&out->obj, 0, sizeof out->obj);
-    out->obj.has = 1;
-    out->obj.root = C ? node_base : kNoNode;
-    out->obj.ubegin = slot_base;
-    out->obj.ucount = U;
-    out->obj.gamma = up(C ? gamma : 0.0);
-    return true;
-}
-
-std::vector<Hot> records(const std::vector<float>& pos) {
-    std::vector<Hot> hot(pos.size() / 9);
-    for (size_t f = 0; f < hot.size(); ++f) hot[f] = make_hot(&pos[9 * f]);
-    return hot;
-}
 
 // ---- the scene as the device holds it, and the refit's persistent workspace -----------------
 struct Layout {  // what the refit reads of accel_dev.hip's DevObj
@@ -511,31 +218,14 @@ void run_range(const Scene& s, const std::vector<Ray>& rays, size_t begin, size_
 }
 
 Result run(const Scene& s, const std::vector<Ray>& rays) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t nt = std::max<size_t>(1, std::min<size_t>({hw ? hw : 1u, 16u, rays.size() / 64 + 1}));
-    std::vector<Result> part(nt);
-    std::vector<std::thread> th;
-    const size_t chunk = (rays.size() + nt - 1) / nt;
-    for (size_t k = 0; k < nt; ++k)
-        th.emplace_back([&, k] { run_range(s, rays, std::min(rays.size(), k * chunk), std::min(rays.size(), (k + 1) * chunk), part[k]); });
-    for (auto& t : th) t.join();
+    const auto part = [&](size_t begin, size_t end, Result& q) { run_range(s, rays, begin, end, q); };
     Result res;
-    for (const Result& q : part) {
+    for (const Result& q : deal<Result>(rays.size(), part)) {
         res.mismatch += q.mismatch;
         res.hits += q.hits;
         res.scanned += q.scanned;
     }
     return res;
-}
-
-std::vector<Ray> make_rays(const std::vector<float>& pos, size_t nrays) {
-    std::vector<Ray> rays;
-    sphere_rays(rays, nrays, 1.0, 1.0);
-    sphere_rays(rays, nrays / 8, 1.0, 1e-3);
-    sphere_rays(rays, nrays / 8, 1.0, 1e3 / 4.5);
-    sphere_rays(rays, nrays / 8, 1e3 / 3.0, 1.0 / 1e3);
-    adversarial_rays(rays, pos, nrays);
-    return rays;
 }
 
 bool all_kept(const Workspace& w) {
@@ -604,72 +294,6 @@ bool class_change(const char* name, const Meshes& A, const Meshes& B, uint32_t o
                 name, obj, face, (int)kept_b, (int)only, rays.size(), (unsigned long long)r.mismatch, (unsigned long long)r.hits,
                 (unsigned long long)r.scanned, (int)healed, (int)!chk, w.refits);
     return kept_b && only && r.mismatch == 0 && healed && !chk && w.refits == 3;
-}
-
-void scale_face(float* p, double s) {  // about its centroid
-    double c[3];
-    for (int j = 0; j < 3; ++j) c[j] = ((double)p[j] + p[3 + j] + p[6 + j]) / 3.0;
-    for (int k = 0; k < 9; ++k) p[k] = (float)(c[k % 3] + (p[k] - c[k % 3]) * s);
-}
-
-bool load(const char* path, std::vector<float>& pos) {
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long n = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    pos.resize((size_t)n / 4);
-    const size_t got = std::fread(pos.data(), 4, pos.size(), f);
-    std::fclose(f);
-    return got == pos.size() && n > 0 && pos.size() % 9 == 0;
-}
-
-std::vector<float> soup(uint32_t T, double spread, double size) {
-    std::vector<float> pos(9 * (size_t)T);
-    for (uint32_t f = 0; f < T; ++f) {
-        const double c[3] = {uni(-spread, spread), uni(-spread, spread), uni(-spread, spread)};
-        for (int k = 0; k < 9; ++k) pos[9 * (size_t)f + k] = (float)(c[k % 3] + uni(-size, size));
-    }
-    return pos;
-}
-
-// slivers (one edge 1e-4 .. 1e-7 of the others), zero-area faces and a few huge ones among a soup
-std::vector<float> slivers(uint32_t T) {
-    std::vector<float> pos = soup(T, 1.0, 0.2);
-    for (uint32_t f = 0; f < T; f += 3) {
-        float* p = &pos[9 * (size_t)f];
-        const double s = std::pow(10.0, -4.0 - (f / 3) % 4);
-        for (int k = 0; k < 3; ++k) p[6 + k] = (float)(p[k] + s * (p[3 + k] - p[k]) + s * uni(-1, 1) * 0.1);
-        if (f % 15 == 0)
-            for (int k = 0; k < 3; ++k) p[6 + k] = p[3 + k];  // b == c
-        if (f % 33 == 0 && f + 1 < T)
-            for (int k = 0; k < 9; ++k) p[9 + k] *= 40.0f;  // the next face: |n|1 large, unculled
-    }
-    return pos;
-}
-
-// A smooth displacement of `amp` per vertex position (shared vertices stay shared).
-std::vector<float> displaced(const std::vector<float>& pos, double amp) {
-    std::vector<float> out(pos.size());
-    for (size_t v = 0; v < pos.size(); v += 3)
-        for (int j = 0; j < 3; ++j) out[v + j] = (float)(pos[v + j] + amp * std::sin(2.5 * pos[v + (j + 1) % 3] + 0.3));
-    return out;
-}
-
-// The sliver mesh's plain faces moved rigidly, each by a smooth function of its centroid; the
-// slivers, the zero-area faces and the huge ones stay where they are, among faces that moved.
-std::vector<float> slivers_moved(const std::vector<float>& pos, double amp) {
-    std::vector<float> out = pos;
-    const uint32_t T = (uint32_t)(pos.size() / 9);
-    for (uint32_t f = 0; f < T; ++f) {
-        if (f % 3 == 0 || (f >= 1 && (f - 1) % 33 == 0)) continue;
-        float* p = &out[9 * (size_t)f];
-        double c[3], d[3];
-        for (int j = 0; j < 3; ++j) c[j] = ((double)p[j] + p[3 + j] + p[6 + j]) / 3.0;
-        for (int j = 0; j < 3; ++j) d[j] = amp * std::sin(2.5 * c[(j + 1) % 3] + 0.3);
-        for (int k = 0; k < 9; ++k) p[k] = (float)(p[k] + d[k % 3]);
-    }
-    return out;
 }
 
 }  // namespace

@@ -11,14 +11,12 @@ sources compiled with -fsanitize=address,undefined run a smaller count as a prog
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
-import numpy as np
 import pytest
 
-from eray_amd import capi, meshgen
-from eray_amd import build as B
+from eray_amd import capi
+from tests.accel_emul import SANITIZER_FLAGS, asan_build, assert_clean_sanitizer_run, figures, run_built, write_spheres
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "eray_hip.h")).read()
@@ -27,33 +25,12 @@ SOURCES = [os.path.join(ROOT, "tests", "cpp", "accel_walk_main.cpp"), os.path.jo
 
 @pytest.fixture(scope="module")
 def sphere_files(tmp_path_factory):
-    d = tmp_path_factory.mktemp("accel_meshes")
-    out = []
-    for T in (2000, 20000):
-        v, _, _, F, _, _ = meshgen.displaced_sphere(T, 42)
-        path = str(d / f"sphere{T}.bin")
-        v[F].reshape(T, 9).astype(np.float32).tofile(path)
-        out.append(path)
-    return out
-
-
-def figures(stdout):
-    """{suite: {name: value}} of the program's 'suite=...' lines."""
-    out = {}
-    for line in stdout.splitlines():
-        if line.startswith("suite="):
-            kv = dict(item.split("=", 1) for item in line.split())
-            name = kv.pop("suite")
-            out[name] = {k: float(v) for k, v in kv.items()}
-    return out
+    return write_spheres(tmp_path_factory.mktemp("accel_meshes"), (2000, 20000))
 
 
 @pytest.fixture(scope="module")
 def walk(sphere_files):
-    exe = os.path.join(ROOT, "eray_amd", "bin", "accel_walk_main")
-    assert exe in B.build_host() and os.access(exe, os.X_OK)
-    r = subprocess.run([exe, *sphere_files, "50000"], capture_output=True, text=True, timeout=900)
-    print(r.stdout)
+    r = run_built("accel_walk_main", [*sphere_files, "50000"], timeout=900)
     return r, figures(r.stdout)
 
 
@@ -122,14 +99,10 @@ def test_moved_meshes_and_scaled_directions(walk, name):
 
 def test_walk_program_under_asan_ubsan(sphere_files, tmp_path):
     """The same two sources with -fsanitize=address,undefined, run directly (its own main)."""
-    cxx = shutil.which("g++") or "g++"
     exe = str(tmp_path / "accel_walk_asan")
-    flags = [f for f in B.ACCEL_WALK_FLAGS if f != "-O2"]
-    subprocess.run([cxx, *flags, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *SOURCES,
-                    "-o", exe], check=True, capture_output=True, text=True)
+    asan_build(SOURCES, exe, SANITIZER_FLAGS)
     r = subprocess.run([exe, *sphere_files, "1500"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and r.stdout.rstrip().endswith("OK"), r.stdout + r.stderr[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert_clean_sanitizer_run(r)
 
 
 # ------------------------------------------------------------------ the boundary -------------

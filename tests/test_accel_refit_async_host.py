@@ -14,12 +14,11 @@ import os
 import re
 import subprocess
 
-import numpy as np
 import pytest
 
-from eray_amd import capi, meshgen
+from eray_amd import capi
 from eray_amd import build as B
-from tests.test_accel_refit_host import asan_build
+from tests.accel_emul import SANITIZER_FLAGS, asan_build, assert_clean_sanitizer_run, figures, run_built, write_spheres
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "eray_hip.h")).read()
@@ -31,28 +30,12 @@ CLASS_CHANGES = {"culled_face_scaled_until_n1_is_4": 0, "nan_vertex_on_a_culled_
 
 @pytest.fixture(scope="module")
 def sphere_file(tmp_path_factory):
-    v, _, _, F, _, _ = meshgen.displaced_sphere(2000, 42)
-    path = str(tmp_path_factory.mktemp("accel_refit_async_meshes") / "sphere2000.bin")
-    v[F].reshape(2000, 9).astype(np.float32).tofile(path)
-    return path
-
-
-def figures(stdout, key):
-    out = {}
-    for line in stdout.splitlines():
-        if line.startswith(key + "="):
-            kv = dict(item.split("=", 1) for item in line.split())
-            name = kv.pop(key)
-            out[name] = {k: float(v) for k, v in kv.items()}
-    return out
+    return write_spheres(tmp_path_factory.mktemp("accel_refit_async_meshes"), (2000,))[0]
 
 
 @pytest.fixture(scope="module")
 def emulation(sphere_file):
-    exe = os.path.join(ROOT, "eray_amd", "bin", "accel_refit_async_main")
-    assert exe in B.build_host() and os.access(exe, os.X_OK)
-    r = subprocess.run([exe, sphere_file, "50000"], capture_output=True, text=True, timeout=900)
-    print(r.stdout)
+    r = run_built("accel_refit_async_main", [sphere_file, "50000"], timeout=900)
     return r, figures(r.stdout, "reuse"), figures(r.stdout, "class_change")
 
 
@@ -86,10 +69,9 @@ def test_a_class_change_fails_that_object_alone_and_heals(emulation):
 
 def test_emulation_under_asan_ubsan(sphere_file, tmp_path):
     exe = str(tmp_path / "accel_refit_async_asan")
-    asan_build(SOURCES, exe, [f for f in B.ACCEL_WALK_FLAGS if f != "-O2"])
+    asan_build(SOURCES, exe, SANITIZER_FLAGS)
     r = subprocess.run([exe, sphere_file, "1500"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and r.stdout.rstrip().endswith("OK"), r.stdout + r.stderr[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert_clean_sanitizer_run(r)
 
 
 # ------------------------------------------------------------------ the boundary -------------
