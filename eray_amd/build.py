@@ -108,6 +108,7 @@ WALK_MAIN = os.path.join(TESTS_CPP, "accel_walk_main.cpp")
 DEV_MAIN = os.path.join(TESTS_CPP, "accel_dev_main.cpp")
 REFIT_MAIN = os.path.join(TESTS_CPP, "accel_refit_main.cpp")
 REFIT_ASYNC_MAIN = os.path.join(TESTS_CPP, "accel_refit_async_main.cpp")
+REFIT_HOSTTREE_MAIN = os.path.join(TESTS_CPP, "accel_refit_hosttree_main.cpp")
 # tests/cpp/update_args_main.cpp (headers only)
 UPDATE_ARGS_MAIN = os.path.join(TESTS_CPP, "update_args_main.cpp")
 UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "include", "eray_hip.h")]
@@ -116,7 +117,8 @@ UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
     the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
-    accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_async_main, update_args_main).  Plain g++: the
+    test_refit_hosttree, accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_hosttree_main, accel_refit_async_main,
+    update_args_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -154,7 +156,8 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
                       ("test_accel", os.path.join(ROOT, "tests", "cpp", "test_accel.cpp")),
                       ("test_accel_dev", os.path.join(ROOT, "tests", "cpp", "test_accel_dev.cpp")),
                       ("test_reach", os.path.join(ROOT, "tests", "cpp", "test_reach.cpp")),
-                      ("test_update", os.path.join(ROOT, "tests", "cpp", "test_update.cpp"))):
+                      ("test_update", os.path.join(ROOT, "tests", "cpp", "test_update.cpp")),
+                      ("test_refit_hosttree", os.path.join(ROOT, "tests", "cpp", "test_refit_hosttree.cpp"))):
         exe = os.path.join(BIN_DIR, name)
         if force or not _newer(exe, [src, HOST_LIB] + headers):
             run([cxx, *flags, src, "-o", exe, "-L" + LIB_DIR, "-leray_host", *link])
@@ -167,6 +170,7 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     for name, main_src, more in (("accel_walk_main", WALK_MAIN, [os.path.join(CSRC, "accel_build.cpp")]),
                                  ("accel_dev_main", DEV_MAIN, ACCEL_DEV_SOURCES),
                                  ("accel_refit_main", REFIT_MAIN, ACCEL_DEV_SOURCES),
+                                 ("accel_refit_hosttree_main", REFIT_HOSTTREE_MAIN, ACCEL_DEV_SOURCES),
                                  ("accel_refit_async_main", REFIT_ASYNC_MAIN, ACCEL_DEV_SOURCES)):
         exe = os.path.join(BIN_DIR, name)
         if force or not _newer(exe, [main_src, *more, *accel_deps]):

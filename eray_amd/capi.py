@@ -229,6 +229,7 @@ SIGNATURES = {
     "eray_rays_reach_light": (C.c_int, [_P, C.POINTER(ReachParams)]),
     "eray_scene_build_ray_accel": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
     "eray_scene_build_ray_accel_device": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
+    "eray_scene_build_ray_accel_refittable": (C.c_int, [_P, _U, C.POINTER(RayAccelInfo)]),
     "eray_scene_drop_ray_accel": (C.c_int, [_P]),
     "eray_render_frames": (C.c_int, [_P, C.POINTER(RenderParams), _U, C.POINTER(C.c_float)]),
     "eray_render_prepare": (C.c_int, [_P, C.POINTER(RenderParams), _U]),
@@ -285,7 +286,8 @@ DEBUG_SIGNATURES = {
 # Entry points a library selected by ERAY_LIB may predate (scripts/rays_bench.py --secondary runs the
 # parent commit's build): absent there, they stay unbound; the product library must have them all.
 _AB_OPTIONAL = {"eray_rays_reach_light", "eray_scene_update_object", "eray_scene_refit_ray_accel",
-                "eray_scene_object_triangle_count", "eray_scene_refit_ray_accel_async", "eray_scene_ray_accel_refit_status"}
+                "eray_scene_object_triangle_count", "eray_scene_refit_ray_accel_async", "eray_scene_ray_accel_refit_status",
+                "eray_scene_build_ray_accel_refittable"}
 
 _lib = None
 
@@ -661,7 +663,10 @@ class Context:
     def refit_ray_accel(self) -> dict:
         """eray_scene_refit_ray_accel: the hierarchy made valid for the current geometry — the
         device build's topology kept when only update_object happened since (rebuilt == 0), else a
-        device build (rebuilt == 1).  Returns eray_ray_accel_info's fields plus refitted, rebuilt."""
+        device build (rebuilt == 1).  After build_ray_accel(refittable=True) the host-built tree's
+        topology is kept on the same terms, and where the call must rebuild it rebuilds with that
+        builder (rebuilt == 1, still host-split and refittable).  Returns eray_ray_accel_info's
+        fields plus refitted, rebuilt."""
         info = RayAccelRefitInfo()
         self._check(lib().eray_scene_refit_ray_accel(self._h, C.byref(info)))
         out = {name: getattr(info.accel, name) for name, _ in RayAccelInfo._fields_}
@@ -669,8 +674,8 @@ class Context:
         return out
 
     def refit_ray_accel_async(self) -> None:
-        """eray_scene_refit_ray_accel_async: the kept-topology refit of a device-built hierarchy enqueued
-        on the context's stream — after its first call outside a capture no copy, no wait, no
+        """eray_scene_refit_ray_accel_async: the kept-topology refit of a device-built hierarchy, or of
+        a host-built one made with build_ray_accel(refittable=True), enqueued on the context's stream — after its first call outside a capture no copy, no wait, no
         allocation, so it is captured with update_object_device before it and the queries after it.  The
         device decides per covered object; refit_status() tells.  Never rebuilds: ErayError
         (E_INVALID_ARGUMENT) where refit_ray_accel would."""
@@ -715,14 +720,20 @@ class Context:
         p = RaysParams(rays_ptr or None, count, object, bounces, flags, out_hit or None, out_rgb or None)
         self._check(lib().eray_cast_rays(self._h, C.byref(p)))
 
-    def build_ray_accel(self, min_faces: int = 0, device: bool = False) -> dict:
+    def build_ray_accel(self, min_faces: int = 0, device: bool = False, refittable: bool = False) -> dict:
         """eray_scene_build_ray_accel: a hierarchy for cast_rays over the objects of at least
         min_faces faces (0: the library's default); synchronous.  device=True builds it on the GPU
         from the resident records (eray_scene_build_ray_accel_device) instead of on the host.
-        Returns eray_ray_accel_info's fields.  Any geometry change drops it; drop_ray_accel
-        releases it."""
+        refittable=True is the host build with what a refit needs kept beside it
+        (eray_scene_build_ray_accel_refittable): the same arrays, and refit_ray_accel /
+        refit_ray_accel_async then keep its topology; with device=True a ValueError, since a device
+        build is always refittable.  Returns eray_ray_accel_info's fields.  Any geometry change
+        drops it; drop_ray_accel releases it."""
+        if device and refittable:
+            raise ValueError("refittable=True is the host build's option: a device build is always refittable")
         info = RayAccelInfo()
-        fn = lib().eray_scene_build_ray_accel_device if device else lib().eray_scene_build_ray_accel
+        fn = (lib().eray_scene_build_ray_accel_device if device else
+              lib().eray_scene_build_ray_accel_refittable if refittable else lib().eray_scene_build_ray_accel)
         self._check(fn(self._h, min_faces, C.byref(info)))
         return {name: getattr(info, name) for name, _ in RayAccelInfo._fields_}
 

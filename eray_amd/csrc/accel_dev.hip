@@ -23,7 +23,9 @@
 // hierarchy's own index array, object_kernel — no scan, no keys, no sort, no allocation that stays.
 // accel_refit_enqueue is that refit with the host taken out (a persistent workspace, the verdict by
 // refit_object_kernel, the levels of at most kBlock nodes by refit_top_levels_kernel in one launch):
-// kernels on the stream only, so that a graph can hold it.
+// kernels on the stream only, so that a graph can hold it.  Both also refit a tree the host builder
+// made (eray_scene_build_ray_accel_refittable): the same shape numbered in recursion order, for which
+// the level kernels have a second instantiation (…_preorder_kernel) picked by the layout's numbering.
 //
 // The host reads back 16 B of counters per covered object after key_kernel (it needs the culled
 // counts to size the node array and lay out the levels); nothing else crosses the bus.
@@ -231,16 +233,37 @@ __global__ __launch_bounds__(kBlock) void refit_check_kernel(const TriHot* __res
 // its first culled slot (a leaf's slots hold its range of the order, ascending; make_leaf re-sorts
 // them), bias 0.  `index` is read and written — each lane reads its leaves' ranges before it
 // writes them, and no two lanes share a range — so neither pointer is __restrict__.
+// Numbering: accel_layout.hpp's LevelOrder for a device build, PreOrder for a refittable host build
+// (its leaves lie in range order, so its index array is the sorted order just the same).
+template <class Numbering>
+__device__ __forceinline__ void refit_level(uint32_t level, uint32_t obj0, const TriHot* __restrict__ tris,
+                                            const DevObj* __restrict__ objs, const double* __restrict__ alpha_beta,
+                                            accel::Node* nodes, accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
+                                            uint32_t* index) {
+    const DevObj ob = objs[obj0 + blockIdx.y];
+    const accel::TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
+    accel::level_node<Numbering>(t, level, blockIdx.x * kBlock + threadIdx.x, index + ob.gbegin + ob.U, 0u,
+                                 reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin, alpha_beta + 2 * (size_t)ob.gbegin,
+                                 ob.node_base, ob.gbegin + ob.U, nodes, bounds, hot, index);
+}
+
 __global__ __launch_bounds__(kBlock) void refit_level_kernel(uint32_t level, uint32_t obj0, const TriHot* __restrict__ tris,
                                                              const DevObj* __restrict__ objs,
                                                              const double* __restrict__ alpha_beta, accel::Node* nodes,
                                                              accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
                                                              uint32_t* index) {
-    const DevObj ob = objs[obj0 + blockIdx.y];
-    const accel::TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
-    accel::level_node(t, level, blockIdx.x * kBlock + threadIdx.x, index + ob.gbegin + ob.U, 0u,
-                      reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin, alpha_beta + 2 * (size_t)ob.gbegin, ob.node_base,
-                      ob.gbegin + ob.U, nodes, bounds, hot, index);
+    refit_level<accel::LevelOrder>(level, obj0, tris, objs, alpha_beta, nodes, bounds, hot, index);
+}
+
+// The same for trees numbered in recursion order: a level's nodes are not contiguous, so its 48-B
+// node and 64-B bounds stores scatter over the tree's node range.
+__global__ __launch_bounds__(kBlock) void refit_level_preorder_kernel(uint32_t level, uint32_t obj0,
+                                                                      const TriHot* __restrict__ tris,
+                                                                      const DevObj* __restrict__ objs,
+                                                                      const double* __restrict__ alpha_beta, accel::Node* nodes,
+                                                                      accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
+                                                                      uint32_t* index) {
+    refit_level<accel::PreOrder>(level, obj0, tris, objs, alpha_beta, nodes, bounds, hot, index);
 }
 
 __global__ __launch_bounds__(kBlock) void object_kernel(const DevObj* __restrict__ objs, uint32_t nobj,
@@ -276,22 +299,42 @@ __global__ __launch_bounds__(kBlock) void refit_reset_kernel(DevAcc* __restrict_
 // agent-scope acquire is needed, and nodes / bounds / index carry no __restrict__, so the compiler
 // neither moves nor keeps a load across the fence in __syncthreads().  The bytes are those of the
 // per-level passes: the same level_node per (level, lane), each level complete before the next.
-__global__ __launch_bounds__(kBlock) void refit_top_levels_kernel(uint32_t first_deep, uint32_t obj0, const TriHot* __restrict__ tris,
-                                                                  const DevObj* __restrict__ objs,
-                                                                  const double* __restrict__ alpha_beta, accel::Node* nodes,
-                                                                  accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
-                                                                  uint32_t* index) {
+// Under either numbering: which ids the children have changes where a lane reads, not who wrote it
+// (a lane of this workgroup, one level earlier) nor through what (global memory).
+template <class Numbering>
+__device__ __forceinline__ void refit_top_levels(uint32_t first_deep, uint32_t obj0, const TriHot* __restrict__ tris,
+                                                 const DevObj* __restrict__ objs, const double* __restrict__ alpha_beta,
+                                                 accel::Node* nodes, accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
+                                                 uint32_t* index) {
     static_assert(kBlock == accel::kTopBlock, "a level of at most kTopBlock nodes per workgroup");
     const DevObj ob = objs[obj0 + blockIdx.x];
     const accel::TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
     for (uint32_t level = first_deep; level-- > 0;) {  // (workgroup-uniform: every lane meets every barrier)
-        accel::level_node(t, level, threadIdx.x, index + ob.gbegin + ob.U, 0u, reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin,
-                          alpha_beta + 2 * (size_t)ob.gbegin, ob.node_base, ob.gbegin + ob.U, nodes, bounds, hot, index);
+        accel::level_node<Numbering>(t, level, threadIdx.x, index + ob.gbegin + ob.U, 0u,
+                                     reinterpret_cast<const accel::Hot*>(tris) + ob.hot_begin, alpha_beta + 2 * (size_t)ob.gbegin,
+                                     ob.node_base, ob.gbegin + ob.U, nodes, bounds, hot, index);
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(kBlock) void refit_top_levels_kernel(uint32_t first_deep, uint32_t obj0, const TriHot* __restrict__ tris,
+                                                                  const DevObj* __restrict__ objs,
+                                                                  const double* __restrict__ alpha_beta, accel::Node* nodes,
+                                                                  accel::NodeBounds* bounds, accel::Hot* __restrict__ hot,
+                                                                  uint32_t* index) {
+    refit_top_levels<accel::LevelOrder>(first_deep, obj0, tris, objs, alpha_beta, nodes, bounds, hot, index);
+}
+
+__global__ __launch_bounds__(kBlock) void refit_top_levels_preorder_kernel(uint32_t first_deep, uint32_t obj0,
+                                                                           const TriHot* __restrict__ tris,
+                                                                           const DevObj* __restrict__ objs,
+                                                                           const double* __restrict__ alpha_beta,
+                                                                           accel::Node* nodes, accel::NodeBounds* bounds,
+                                                                           accel::Hot* __restrict__ hot, uint32_t* index) {
+    refit_top_levels<accel::PreOrder>(first_deep, obj0, tris, objs, alpha_beta, nodes, bounds, hot, index);
 }
 
 // The verdict the synchronous refit takes on the host, taken here: per covered object the counters
@@ -332,6 +375,9 @@ struct Arena {
         const hipError_t e_ = (expr);   \
         if (e_ != hipSuccess) return e_; \
     } while (0)
+
+// The numbering of a layout's trees (one build call made them all): recursion order or level order.
+bool preorder(const std::vector<DevObj>& objs) { return !objs.empty() && objs.front().numbering == 1u; }
 
 }  // namespace
 
@@ -515,11 +561,12 @@ hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, 
     info->max_depth = ra.max_depth;
     if (P) {
         accel::NodeBounds* d_bounds = a.at<accel::NodeBounds>(o_bounds);
+        const auto level_pass = preorder(objs) ? refit_level_preorder_kernel : refit_level_kernel;
         for (uint32_t level = ra.max_depth; level-- > 0;) {
             const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
             for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
-                refit_level_kernel<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes,
-                                                                                             d_bounds, ra.hot, ra.index);
+                level_pass<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes, d_bounds,
+                                                                                     ra.hot, ra.index);
                 TRY(hipGetLastError());
             }
         }
@@ -569,12 +616,16 @@ hipError_t accel_refit_workspace(RayAccel& ra, hipStream_t s) {
 }
 
 // Memory safety of the level passes whatever the faces hold (they run before the verdict is known
-// to anyone): level_node takes every range from the layout (node_range, first_child: C, full,
-// extra), make_leaf indexes faces / alpha_beta by entries of the index array — which the build
-// filled with the object's face indices and which a refit only permutes inside leaf ranges — and
-// stores to slots and node ids computed from the layout; make_inner reads two node ids computed from
-// the layout.  No face value (NaN, infinite, huge) reaches an index: such values end in boxes and
-// margins of an object whose record then says has = 0.
+// to anyone): level_node takes every range from the layout (node_range: C, full, extra) and every
+// node id from its numbering (LevelOrder: node_id, first_child; PreOrder: id, subtree_nodes — both
+// arithmetic on C, the level and the lane, below the tree's node count, which the build's node array
+// holds from node_base on), make_leaf indexes faces / alpha_beta by entries of the index array — which
+// the build filled with the object's face indices and which a refit only permutes inside leaf ranges
+// — and stores to slots and node ids computed from the layout; make_inner reads two node ids computed
+// from the layout.  No face value (NaN, infinite, huge) reaches an index: such values end in boxes
+// and margins of an object whose record then says has = 0.  A host-built tree qualifies on the same
+// terms: capi.cpp records its layout only after checking that its node count and depth are
+// tree_layout(C)'s.
 hipError_t accel_refit_enqueue(const TriHot* d_hot, RayAccel& ra, hipStream_t s) {
     const RefitWorkspace& ws = ra.refit;
     const uint32_t ncov = ws.ncov;
@@ -597,17 +648,20 @@ hipError_t accel_refit_enqueue(const TriHot* d_hot, RayAccel& ra, hipStream_t s)
     }
     if (ra.node_count) {
         const uint32_t first_deep = ra.refit_top_levels ? ws.first_deep : 0u;
+        const bool pre = preorder(ra.layout);
+        const auto level_pass = pre ? refit_level_preorder_kernel : refit_level_kernel;
+        const auto top_pass = pre ? refit_top_levels_preorder_kernel : refit_top_levels_kernel;
         for (uint32_t level = ra.max_depth; level-- > first_deep;) {
             const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
             for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
-                refit_level_kernel<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes,
-                                                                                             d_bounds, ra.hot, ra.index);
+                level_pass<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes, d_bounds,
+                                                                                     ra.hot, ra.index);
                 TRY(hipGetLastError());
             }
         }
         if (first_deep) {
-            refit_top_levels_kernel<<<ncov, kBlock, 0, s>>>(std::min(first_deep, ra.max_depth), 0u, d_hot, d_objs, d_ab, ra.nodes, d_bounds,
-                                                            ra.hot, ra.index);
+            top_pass<<<ncov, kBlock, 0, s>>>(std::min(first_deep, ra.max_depth), 0u, d_hot, d_objs, d_ab, ra.nodes, d_bounds, ra.hot,
+                                             ra.index);
             TRY(hipGetLastError());
         }
     }

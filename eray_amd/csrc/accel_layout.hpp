@@ -15,7 +15,8 @@
 // are `extra` = C - kLeafFaces * 2^F such nodes when floor(C / 2^F) == kLeafFaces; the one at
 // position j starts at lo = kLeafFaces * j + (how many of them precede it), so its children are
 // numbered 2^(F+1) - 1 + 2 (lo - kLeafFaces j) and the next.  Node count and depth are the host
-// build's for the same C.
+// build's for the same C.  The host build numbers the same shape in recursion order instead
+// (PreOrder below): with it level_node refits a host-built tree, whose leaves lie in range order.
 #pragma once
 
 #include "accel_margin.hpp"
@@ -95,6 +96,59 @@ ERAY_HD uint32_t node_id(uint32_t L, uint32_t j) { return (1u << L) - 1u + j; }
 ERAY_HD uint32_t first_child(const TreeLayout& t, uint32_t L, uint32_t j, uint32_t lo) {
     return L < t.full ? node_id(L + 1, 2 * j) : node_id(t.full + 1, 0) + 2u * (lo - kLeafFaces * j);
 }
+
+// tree_layout(n).nodes for n >= 1 without the loop: with b = floor(log2 n) (n > kLeafFaces), n >> (b - 2)
+// is in 4 .. 7; when it is kLeafFaces = 4 the complete levels end at F = b - 2 and n - (4 << F) nodes
+// split once more, otherwise at F = b - 1 (n >> F is 2 or 3) and none does.
+static_assert(kLeafFaces == 4, "subtree_nodes' closed form");
+ERAY_HD uint32_t subtree_nodes(uint32_t n) {
+    if (n <= kLeafFaces) return 1u;
+    const uint32_t b = 31u - (uint32_t)__builtin_clz(n);
+    const bool four = (n >> (b - 2u)) == kLeafFaces;
+    const uint32_t F = four ? b - 2u : b - 1u;
+    return (2u << F) - 1u + (four ? 2u * (n - (kLeafFaces << F)) : 0u);
+}
+
+// NUMBERING.  Which local id the node j of the complete level L gets, and its two children (the
+// first half's first), is a compile-time policy of level_node; the topology, the ranges and the
+// slots are the same under both.  Either way every id is a function of C, L and j alone.
+//
+// LevelOrder: the device builder's (accel_dev.hip level_kernel), level by level as described above.
+struct LevelOrder {
+    static ERAY_HD uint32_t id(uint32_t, uint32_t L, uint32_t j) { return node_id(L, j); }
+    static ERAY_HD void children(const TreeLayout& t, uint32_t L, uint32_t j, uint32_t lo, uint32_t, uint32_t, uint32_t& c0,
+                                 uint32_t& c1) {
+        c0 = first_child(t, L, j, lo);
+        c1 = c0 + 1u;
+    }
+};
+
+// PreOrder: the host builder's (accel_build.cpp build_node pushes a node, then its first half's
+// subtree, then its second half's).  The root is 0; a node `me` over n faces has its first child at
+// me + 1 and its second at me + 1 + subtree_nodes(n / 2).  id() walks the halves node_range walks:
+// O(L) steps per lane, no table, no scratch.
+struct PreOrder {
+    static ERAY_HD uint32_t id(uint32_t C, uint32_t L, uint32_t j) {
+        uint32_t me = 0, n = C;
+        for (uint32_t k = L; k-- > 0;) {
+            const uint32_t half = n / 2;
+            if ((j >> k) & 1u) {
+                me += 1u + subtree_nodes(half);
+                n -= half;
+            } else {
+                me += 1u;
+                n = half;
+            }
+        }
+        return me;
+    }
+    // me: id(C, L, j); n: the node's count (node_range), above kLeafFaces
+    static ERAY_HD void children(const TreeLayout&, uint32_t, uint32_t, uint32_t, uint32_t n, uint32_t me, uint32_t& c0,
+                                 uint32_t& c1) {
+        c0 = me + 1u;
+        c1 = c0 + subtree_nodes(n / 2);
+    }
+};
 
 // A node's real box and margins before rounding (temporary, one per node).
 struct NodeBounds {
@@ -179,7 +233,10 @@ ERAY_HD void make_inner(uint32_t l, uint32_t r, const Node* nodes, const NodeBou
 // (level == t.full + 1) the two leaves under node j of level t.full when it splits once more.
 // Levels are run deepest first, so an inner node finds its children written.  sorted: the culled
 // faces in (key, index) order, each entry its original index + id_bias; slot0: the slot of
-// sorted[0]; nodes / bounds are the scene's, the tree's node k at node_base + k.
+// sorted[0]; nodes / bounds are the scene's, the tree's node k at node_base + k, k by Numbering.
+// Every node id, range and slot below comes from C, full, extra, level and j; none from a face
+// value or from what `sorted` holds (accel_dev.hip accel_refit_enqueue relies on it).
+template <class Numbering = LevelOrder>
 ERAY_HD void level_node(const TreeLayout& t, uint32_t level, uint32_t j, const uint32_t* sorted, uint32_t id_bias,
                         const Hot* faces, const double* alpha_beta, uint32_t node_base, uint32_t slot0, Node* nodes,
                         NodeBounds* bounds, Hot* hot, uint32_t* index) {
@@ -189,15 +246,18 @@ ERAY_HD void level_node(const TreeLayout& t, uint32_t level, uint32_t j, const u
     if (j >= (1u << L)) return;
     uint32_t lo, n;
     node_range(t.C, L, j, lo, n);
-    uint32_t first[2] = {lo, lo + n / 2}, count[2] = {n, 0u}, id[2] = {node_base + node_id(L, j), 0u};
+    const uint32_t me = Numbering::id(t.C, L, j);
+    uint32_t first[2] = {lo, lo + n / 2}, count[2] = {n, 0u}, id[2] = {node_base + me, 0u};
     uint32_t leaves = n <= kLeafFaces ? 1u : 0u;
+    uint32_t c0 = 0, c1 = 0;  // the children, local ids
+    if (n > kLeafFaces) Numbering::children(t, L, j, lo, n, me, c0, c1);
     if (pairs) {
         if (n <= kLeafFaces) return;
         leaves = 2;
         count[0] = n / 2;
         count[1] = n - n / 2;
-        id[0] = node_base + first_child(t, L, j, lo);
-        id[1] = id[0] + 1;
+        id[0] = node_base + c0;
+        id[1] = node_base + c1;
     }
     for (uint32_t k = 0; k < 2; ++k) {
         if (k >= leaves) break;
@@ -210,10 +270,9 @@ ERAY_HD void level_node(const TreeLayout& t, uint32_t level, uint32_t j, const u
         bounds[id[k]] = nb;
     }
     if (leaves) return;
-    const uint32_t c0 = node_base + first_child(t, L, j, lo);
     Node nd;
     NodeBounds nb;
-    make_inner(c0, c0 + 1, nodes, bounds, nd, nb);
+    make_inner(node_base + c0, node_base + c1, nodes, bounds, nd, nb);
     nodes[id[0]] = nd;
     bounds[id[0]] = nb;
 }

@@ -22,6 +22,7 @@
 #include "accel_build.hpp"
 #include "accel_check.hpp"
 #include "accel_dev.hpp"
+#include "accel_layout.hpp"
 #include "internal.hpp"
 #include "owners.hpp"
 #include "rays_args.hpp"
@@ -1432,13 +1433,16 @@ int eray_rays_reach_light(eray_ctx* ctx, const eray_reach_params* rp) {
     return ERAY_OK;
 }
 
-// The ray-query hierarchy (accel_build.hpp): built on the host from the device's own TriHot
-// records — the bits the kernels test — and uploaded; synchronous.
-int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
-    if (int st = use_device(ctx)) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = sync_scene(ctx)) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
+}  // extern "C"
+
+namespace {
+// The ray-query hierarchy (accel_build.hpp) built on the host from the device's own TriHot records
+// — the bits the kernels test — and uploaded, once the scene is uploaded and the stream idle.
+// refittable: the layout a refit needs is recorded as well (AccelDevLayout per covered object, from
+// the Built results; numbering 1: the host builder's recursion order); the arrays are the same.
+int build_accel_host(eray_ctx* ctx, uint32_t min_faces, std::chrono::steady_clock::time_point t0, eray_ray_accel_info* info,
+                     bool refittable) {
+    const char* const fn = refittable ? "eray_scene_build_ray_accel_refittable" : "eray_scene_build_ray_accel";
     ctx->ray_accel.drop();
     if (!min_faces) min_faces = 2 * kRayTile;
     const uint32_t T = ctx->total_tris;
@@ -1450,7 +1454,8 @@ int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel
     std::vector<eray::accel::Hot> leaf;
     std::vector<uint32_t> index;
     eray_ray_accel_info out{};
-    uint32_t begin = 0;
+    std::vector<AccelDevLayout> layout;
+    uint32_t begin = 0, blocks = 0, culled = 0;
     for (size_t i = 0; i < ctx->objects.size(); ++i) {
         const uint32_t n = ctx->objects[i].T;
         std::memset(&objs[i], 0, sizeof objs[i]);
@@ -1460,8 +1465,18 @@ int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel
             if (nodes.size() + 2 * (size_t)n > 0x7fffffffu || leaf.size() + n > 0x7fffffffu ||
                 !eray::accel::build_object(hot.data() + begin, n, (uint32_t)nodes.size(), (uint32_t)leaf.size(),
                                      eray::accel::kStackDepth, &b, &why))
-                return set_error(ctx, ERAY_E_UNSUPPORTED, "eray_scene_build_ray_accel: object %zu: %s", i,
-                                 *why ? why : "too many nodes");
+                return set_error(ctx, ERAY_E_UNSUPPORTED, "%s: object %zu: %s", fn, i, *why ? why : "too many nodes");
+            if (refittable) {
+                // the refit's kernels take every node id and range from this record: it must describe the tree
+                const uint32_t C = n - b.unculled;
+                const eray::accel::TreeLayout t = eray::accel::tree_layout(C);
+                if (b.nodes.size() != t.nodes || b.depth != t.depth)
+                    return set_error(ctx, ERAY_E_UNSUPPORTED, "%s: object %zu: the tree is not the shape its face count lays out", fn, i);
+                layout.push_back(AccelDevLayout{begin, n, (uint32_t)leaf.size(), blocks, (uint32_t)i, C, b.unculled, culled,
+                                                (uint32_t)nodes.size(), t.full, t.extra, 1u});
+                blocks += (n + 255u) / 256u;  // (accel_dev.hip's workgroups of 256 faces)
+                culled += C;
+            }
             objs[i] = b.obj;
             nodes.insert(nodes.end(), b.nodes.begin(), b.nodes.end());
             leaf.insert(leaf.end(), b.hot.begin(), b.hot.end());
@@ -1492,12 +1507,38 @@ int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel
         ra.min_faces = min_faces;
         ra.node_count = nodes.size();
         ra.slot_count = leaf.size();
-        ra.builder = RayAccel::kHost;
+        ra.builder = refittable ? RayAccel::kHostRefittable : RayAccel::kHost;
+        if (refittable) {
+            ra.layout = std::move(layout);
+            ra.max_depth = out.max_depth;
+        }
         ra.valid = true;
     }
     out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (info) *info = out;
     return ERAY_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// The host build (synchronous).  A refit after it rebuilds on the device; the async refit refuses.
+int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
+    if (int st = use_device(ctx)) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int st = sync_scene(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
+    return build_accel_host(ctx, min_faces, t0, info, false);
+}
+
+// The same build, the same arrays, with what a refit needs kept beside them: the refit calls then
+// keep this tree's topology as they keep a device build's, and rebuild with this builder.
+int eray_scene_build_ray_accel_refittable(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
+    if (int st = use_device(ctx)) return st;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int st = sync_scene(ctx)) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
+    return build_accel_host(ctx, min_faces, t0, info, true);
 }
 
 }  // extern "C"
@@ -1547,12 +1588,13 @@ int build_accel_device(eray_ctx* ctx, uint32_t min_faces, std::chrono::steady_cl
     return ERAY_OK;
 }
 
-// Can a refit keep the topology?  The last build was the device's and covered these objects, at
-// these places, with these face counts, and no object was added and the scene not reset since
-// (objs has a record per object of the build's scene: the arrays fit that scene only).
+// Can a refit keep the topology?  The last build was the device's or the refittable host build and
+// covered these objects, at these places, with these face counts, and no object was added and the
+// scene not reset since (objs has a record per object of the build's scene: the arrays fit that
+// scene only).
 bool same_layout(const eray_ctx* ctx) {
     const RayAccel& ra = ctx->ray_accel;
-    bool same = ra.builder == RayAccel::kDevice && !ra.scene_changed && ra.objs.cap == ctx->objects.size();
+    bool same = ra.refittable() && !ra.scene_changed && ra.objs.cap == ctx->objects.size();
     if (same) {
         const std::vector<AccelDevObject> covered = covered_objects(ctx, ra.min_faces);
         same = covered.size() == ra.layout.size();
@@ -1578,6 +1620,7 @@ int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ra
 
 // Makes the hierarchy valid for the current records: the device build's topology is kept when only
 // eray_scene_update_object happened since (accel_dev.hip accel_refit_device), else a device build.
+// A refittable host build is treated alike: its topology is kept, else it is built again.
 int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
     if (int st = use_device(ctx)) return st;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1587,7 +1630,7 @@ int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
     if (int st = sync_scene(ctx)) return st;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the arrays)
     eray_ray_accel_refit_info out{};
-    const bool same = same_layout(ctx);
+    const bool same = same_layout(ctx), host_refittable = ra.builder == RayAccel::kHostRefittable;
     bool kept = false;
     if (same) {
         AccelDevInfo dev;
@@ -1606,7 +1649,11 @@ int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
         }
     }
     if (!kept) {
-        if (int st = build_accel_device(ctx, ra.min_faces, t0, &out.accel)) return st;
+        // a caller who chose the host split stays on it (and refittable); every other hierarchy
+        // is replaced by a device build
+        if (int st = host_refittable ? build_accel_host(ctx, ra.min_faces, t0, &out.accel, true)
+                                     : build_accel_device(ctx, ra.min_faces, t0, &out.accel))
+            return st;
         out.rebuilt = 1;
     }
     if (info) *info = out;
@@ -1623,7 +1670,7 @@ int eray_scene_refit_ray_accel_async(eray_ctx* ctx) {
     RayAccel& ra = ctx->ray_accel;
     if (ra.builder == RayAccel::kNone)
         return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: the scene has no ray-query hierarchy to refit", fn);
-    if (ra.builder != RayAccel::kDevice)
+    if (!ra.refittable())
         return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: the hierarchy was built on the host (only a device build is refitted)", fn);
     if (!same_layout(ctx))
         return set_error(ctx, ERAY_E_INVALID_ARGUMENT,

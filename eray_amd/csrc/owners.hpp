@@ -114,11 +114,15 @@ struct DeviceBuf : Buffer<T, hipFree> {
 // (a stale tree is never used; eray_scene_refit_ray_accel makes it valid again); the memory is
 // released by drop() or with the owner.
 // A covered object as the device builder laid it out (accel_dev.hip; 48 B, uploaded as it stands).
+// The refittable host build (capi.cpp) derives the same record from its results; cbase is the
+// build's alone.  numbering: how the tree's nodes are numbered — 0 level by level (the device
+// build), 1 in recursion order (the host build); one value per scene.
 struct AccelDevLayout {
     uint32_t hot_begin, faces, gbegin, block_begin;
-    uint32_t index, C, U, cbase;           // C, U, cbase: the culled / unculled counts, first sorted position
-    uint32_t node_base, full, extra, pad;  // (accel_layout.hpp TreeLayout)
+    uint32_t index, C, U, cbase;                 // C, U, cbase: the culled / unculled counts, first sorted position
+    uint32_t node_base, full, extra, numbering;  // (accel_layout.hpp TreeLayout, LevelOrder / PreOrder)
 };
+static_assert(sizeof(AccelDevLayout) == 48, "the kernels' record");
 
 // What eray_scene_refit_ray_accel_async works in (accel_dev.hip accel_refit_workspace): one device
 // allocation that lives from the first eligible call outside a capture until the next build or
@@ -146,9 +150,11 @@ struct RayAccel {
     // what the last build covered (eray_debug_ray_accel_check): its min_faces, node and slot counts
     uint32_t min_faces = 0;
     size_t node_count = 0, slot_count = 0;
-    // which builder made it (kNone: never built, or dropped) and, for the device builder, its host-side
-    // layout and depth: what eray_scene_refit_ray_accel needs to rewrite the levels of the same topology
-    enum Builder : uint32_t { kNone = 0, kHost = 1, kDevice = 2 };
+    // which builder made it (kNone: never built, or dropped) and, for the device builder and the
+    // refittable host build (eray_scene_build_ray_accel_refittable), its host-side layout and depth:
+    // what eray_scene_refit_ray_accel needs to rewrite the levels of the same topology
+    enum Builder : uint32_t { kNone = 0, kHost = 1, kDevice = 2, kHostRefittable = 3 };
+    bool refittable() const { return builder == kDevice || builder == kHostRefittable; }
     Builder builder = kNone;
     std::vector<AccelDevLayout> layout;
     uint32_t max_depth = 0;

@@ -324,11 +324,18 @@ Ray Ray::make(Vector3 start, Vector3 dir) {  // Ray::new (raycasting.rs:16-21): 
 }
 
 Engine::RayAccelInfo Engine::build_ray_accel(uint32_t min_faces, bool on_device) {
+    return build_ray_accel(min_faces, on_device, false);
+}
+
+Engine::RayAccelInfo Engine::build_ray_accel(uint32_t min_faces, bool on_device, bool refittable) {
+    if (on_device && refittable)
+        throw Failure(ERAY_E_INVALID_ARGUMENT, "Engine::build_ray_accel: refittable is the host build's option");
     Device& d = Device::current();
     if (scene_.dirty_) upload();
     eray_ray_accel_info i{};
-    d.check(on_device ? eray_scene_build_ray_accel_device(d.ctx(), min_faces, &i)
-                      : eray_scene_build_ray_accel(d.ctx(), min_faces, &i));
+    d.check(on_device    ? eray_scene_build_ray_accel_device(d.ctx(), min_faces, &i)
+            : refittable ? eray_scene_build_ray_accel_refittable(d.ctx(), min_faces, &i)
+                         : eray_scene_build_ray_accel(d.ctx(), min_faces, &i));
     return RayAccelInfo{i.objects, i.max_depth, i.nodes, i.faces, i.unculled_faces, i.device_bytes, i.build_ms};
 }
 

@@ -157,12 +157,16 @@ public:
     // without scanning every face.  It lasts until the scene changes (scene() marks it changed:
     // the next upload drops it) or drop_ray_accel.  on_device builds it on the GPU from the resident
     // records (eray_scene_build_ray_accel_device) instead of on the host: the same hits either way.
+    // refittable (the three-argument form; false in the other) is the host build with what a refit needs kept beside it
+    // (eray_scene_build_ray_accel_refittable): refit_ray_accel then keeps this tree's topology.  With
+    // on_device it is a failure (ERAY_E_INVALID_ARGUMENT): a device build is always refittable.
     struct RayAccelInfo {
         uint32_t objects, max_depth;
         uint64_t nodes, faces, unculled_faces, device_bytes;
         float build_ms;
     };
     RayAccelInfo build_ray_accel(uint32_t min_faces = 0, bool on_device = false);
+    RayAccelInfo build_ray_accel(uint32_t min_faces, bool on_device, bool refittable);
     void drop_ray_accel();
     // New geometry for object `index` of the scene in place (eray_scene_update_object): the faces
     // (positions, normals, uvs) and the bounding box of `object` replace the scene object's; the
@@ -173,9 +177,10 @@ public:
     // ERAY_E_INVALID_ARGUMENT for an index that is no object or another face count.
     void update_object(size_t index, const Object<Built>& object);
     // The hierarchy made valid for the current geometry (eray_scene_refit_ray_accel): after
-    // update_object alone, on a device-built hierarchy, the tree's topology is kept and its boxes,
+    // update_object alone, on a device-built or refittable host-built hierarchy, the tree's topology is kept and its boxes,
     // margins and face copies are recomputed (the same hits; pruning weakens as the mesh moves away
-    // from the geometry the tree was split for); otherwise it is rebuilt on the device.
+    // from the geometry the tree was split for); otherwise it is rebuilt, by the refittable host
+    // build when that made it, else on the device.
     struct RayAccelRefitInfo {
         RayAccelInfo accel;
         uint32_t refitted;  // objects whose topology was kept

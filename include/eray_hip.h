@@ -598,6 +598,31 @@ typedef struct eray_ray_accel_refit_status {   /*                               
 } eray_ray_accel_refit_status;
 int eray_scene_ray_accel_refit_status(eray_ctx* ctx, eray_ray_accel_refit_status* out);
 
+/* eray_scene_build_ray_accel with what a refit needs kept beside it: the same host build, the same
+ * four device arrays byte for byte, the same info — and, on the host, per covered object the layout
+ * of its tree (face counts by class, node and slot bases, the tree's shape; 48 B) and the depth.
+ * The host builder splits as the device builder does (a range of at most 4 faces is a leaf, else
+ * mid = lo + count / 2), so its tree has the shape the culled face count alone lays out and differs
+ * from a device build's only in the split's order of the faces and in the numbering of the nodes
+ * (recursion order, not level by level); the refit's level kernels have an instantiation for that
+ * numbering.  After this call
+ *   - eray_scene_refit_ray_accel keeps the topology under the conditions it keeps a device build's
+ *     (rebuilt = 0, refitted = covered objects); where it must rebuild — a face changed class, an
+ *     object was added, the scene reset, the covered set changed — it rebuilds with THIS builder
+ *     (rebuilt = 1): the hierarchy stays host-split and refittable;
+ *   - eray_scene_refit_ray_accel_async is eligible as after a device build, with the same workspace,
+ *     per-object verdict, fallback to scanning, healing and refusals.
+ * Measured on MI355X (scripts/rays_refit_host_bench.py): update + refit takes 0.40 ms
+ * at 69,451 faces and 0.65 ms at 1M (0.13 / 0.38 ms as a graph replay), 6-12 % more than on a
+ * device-built tree; 2^20 incoherent rays stay 1.5-2.2x faster through the refitted host tree than
+ * through the refitted device tree, within 2 % of a fresh host build after a smooth displacement of
+ * up to 5 % of the mesh radius and 4-7 % behind it after 20 %.
+ * eray_scene_build_ray_accel itself is unchanged: a refit after it rebuilds on the device and the
+ * async refit refuses.  Synchronous; errors, invalidation and eray_scene_drop_ray_accel as for
+ * eray_scene_build_ray_accel.  Present in builds that define ERAY_HAS_RAY_ACCEL_REFIT_HOST. */
+#define ERAY_HAS_RAY_ACCEL_REFIT_HOST 1
+int eray_scene_build_ray_accel_refittable(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info /* may be NULL */);
+
 /* Engine::reaches_light (engine.rs:218-228) for shadow rays the caller supplies: "does this point
  * see that point" for light baking, visibility probes and a caller's own shading.  Per ray i:
  * dist = |targets[i] - start|; the objects are taken in scene order and the FIRST object whose
