@@ -1040,14 +1040,25 @@ __device__ __forceinline__ void store_slice(const FrameParams& p, const FrameOut
 
 // kStaging: the build keeps the LDS-staged output path (only the dense large-mesh builds, whose
 // 4-slot north-star frames use it; the others store per lane only and carry none of its registers)
-template <bool kCull, bool kLdsTiles, int kMat, bool kStaging = true, typename Scene, typename Mid = NoMid>
+//
+// kOne (LDS-scene builds, the launcher's choice for a scene of one object — main.rs's own shape):
+// the object loops are gone, and with them the closest-object compare, the per-lane object
+// selection and the second tri_begin read; the object's ObjGeom is read once per sub-block and
+// reused by the shadow test, and the light count comes from `counts` (the preloaded nobj |
+// nlights << 16), not from a kernel-argument read per loop.  The MaterialDesc and the lights are
+// still read where they are used: reading them ahead of the search as well, to wait for them once,
+// measured slower — the records held across the search cost more SGPR spills than their round
+// trips.
+template <bool kCull, bool kLdsTiles, int kMat, bool kStaging = true, bool kOne = false, typename Scene,
+          typename Mid = NoMid>
 __device__ __forceinline__ void render_sub(const FrameParams& p, const FrameOut& fo, const CamDev& cam, const RowMap& rm,
                                            const Scene& sc, uint32_t wx0, uint32_t py0,
                                            bool active, TriHot* s_hot, TriCull* s_cull, char* s_bins, float4* s_rgb,
                                            uint32_t* s_ppm, bool aligned, bool has_given = false,
                                            f3 given_d = f3{0.0f, 0.0f, 0.0f}, bool coop = true,
                                            PreRange pre = PreRange{0u, 0u, false}, uint32_t pre_obj = ~0u,
-                                           Mid&& mid = Mid{}) {
+                                           Mid&& mid = Mid{}, uint32_t counts = 0) {
+    static_assert(!kOne || !kLdsTiles, "the single-object path is a small-scene (LDS-scene) build's");
     // coop (workgroup-uniform): the workgroup's four sub-blocks share their large objects' work —
     // binned chunks dealt over the waves, shadow rays through shared LDS tiles — with barriers;
     // otherwise (light sub-blocks) every wave searches its own bins and shadow rays alone
@@ -1080,8 +1091,19 @@ __device__ __forceinline__ void render_sub(const FrameParams& p, const FrameOut&
     float closest = 0.0f, bu = 0.0f, bv = 0.0f, bt = 0.0f;
     uint32_t best_obj = 0;
     int best_face = -1;
-    for (uint32_t oi = 0; oi < p.nobj; ++oi) {
-        const ObjGeom ob = sc.geom(oi);  // uniform
+    // object and light counts; the single-object path's ObjGeom, read once
+    const uint32_t nobj = kOne ? 1u : p.nobj;
+    const uint32_t nlights = kOne ? counts >> 16 : p.nlights;
+    ObjGeom one_ob{};
+    if constexpr (kOne) one_ob = sc.geom(0);
+    auto geom = [&](uint32_t oi) {
+        if constexpr (kOne)
+            return one_ob;
+        else
+            return sc.geom(oi);
+    };
+    for (uint32_t oi = 0; oi < nobj; ++oi) {
+        const ObjGeom ob = geom(oi);  // uniform
         ERAY_TRACE_WAVE0(16);
         const bool direct = !kLdsTiles || ob.tri_count <= kDirectMax;
         const bool wave_bins = kCull && !direct && !coop && ob.bin_start && ob.tri_count <= kWaveBinMaxTris;
@@ -1147,14 +1169,14 @@ __device__ __forceinline__ void render_sub(const FrameParams& p, const FrameOut&
     TriShade sh = TriShade{};
     if (__any(have)) {
         uint32_t g = 0;
-        for (uint32_t oi = 0; oi < p.nobj; ++oi) {
+        for (uint32_t oi = 0; oi < nobj; ++oi) {
             if (!__any(have && best_obj == oi)) continue;
-            const uint32_t tb = load_const(&sc.geom_ptr(oi)->tri_begin, 0);
+            const uint32_t tb = kOne ? one_ob.tri_begin : load_const(&sc.geom_ptr(oi)->tri_begin, 0);
             if (have && best_obj == oi) g = tb + (uint32_t)best_face;
         }
         sh = sc.shade(g);
     }
-    for (uint32_t oi = 0; oi < p.nobj; ++oi) {  // per-lane object, read from uniform copies
+    for (uint32_t oi = 0; oi < nobj; ++oi) {  // per-lane object, read from uniform copies
         if (!__any(have && best_obj == oi)) continue;
         const MaterialDesc mat = sc.mat(oi);
         ERAY_TRACE_WAVE0(17);
@@ -1220,8 +1242,8 @@ __device__ __forceinline__ void render_sub(const FrameParams& p, const FrameOut&
     // Point lights first (engine.rs:130-135), 32 at a time: every light's shadow ray, then the
     // shading of the lights that reach the hit, in list order.  The texture loads above are
     // still in flight during the first shadow scan; the shading is their first use.
-    for (uint32_t li0 = 0; li0 < p.nlights; li0 += 32) {
-        const uint32_t li1 = min(p.nlights, li0 + 32);
+    for (uint32_t li0 = 0; li0 < nlights; li0 += 32) {
+        const uint32_t li1 = min(nlights, li0 + 32);
         uint32_t lit = 0;  // bit li - li0: point light li reaches the lane's hit
         for (uint32_t li = li0; li < li1; ++li) {
             const LightDesc L = sc.light(li);
@@ -1243,8 +1265,8 @@ __device__ __forceinline__ void render_sub(const FrameParams& p, const FrameOut&
                     dist = len(sub(Lp, S));
                 }
             };
-            for (uint32_t oj = 0; oj < p.nobj; ++oj) {
-                const ObjGeom ob = sc.geom(oj);
+            for (uint32_t oj = 0; oj < nobj; ++oj) {
+                const ObjGeom ob = geom(oj);
                 ERAY_TRACE_WAVE0(19);
                 // A point box (the loaded meshes'): when it certainly rejects every lane's shadow
                 // ray (point_box_rejects), bbox_hit is false for all of them — no ray, no face
@@ -1326,7 +1348,7 @@ __device__ __forceinline__ void render_sub(const FrameParams& p, const FrameOut&
     }
     if (have) {
         material();
-        for (uint32_t li = 0; li < p.nlights; ++li) {  // ambient lights (engine.rs:197-209)
+        for (uint32_t li = 0; li < nlights; ++li) {  // ambient lights (engine.rs:197-209)
             const LightDesc L = sc.light(li);
             if (L.variant != 1) continue;
             const rgb m{rust_min(L.color[0], color.r), rust_min(L.color[1], color.g),
@@ -1529,7 +1551,8 @@ __device__ __forceinline__ void fill_frames(const FrameParams& p, uint32_t q, ui
 // bin entries, scalar store offsets) and fits 4 per CU; with the fill at one workgroup per CU
 // (launch_frame_kernel) 3840x2160 / 70k 22.2 -> 20.1 us, its moving camera 50.0 -> 46.7 us.
 constexpr int kDenseWgs = 4;
-template <bool kCull, bool kLdsTiles, int kMat, bool kLdsScene, bool kDense = false, bool kDev = false>
+// kOne (LDS-scene builds): the scene has one object (render_sub's single-object path).
+template <bool kCull, bool kLdsTiles, int kMat, bool kLdsScene, bool kDense = false, bool kDev = false, bool kOne = false>
 __global__ void __launch_bounds__(kWG, (kMat & kMatSpecPow) ? 1 : (kLdsTiles && !kDense) ? 1 : (kDense ? kDenseWgs : 3))  // 3 workgroups per CU where that fits
     frame_kernel(const ObjectDesc* h_objects, const LightDesc* h_lights, const TriCull* h_cull, const TriHot* h_tris,
                  const void* h_aux, uint32_t h_counts, uint32_t h_total_tris, uint32_t h_total_sub,
@@ -1730,9 +1753,10 @@ __global__ void __launch_bounds__(kWG, (kMat & kMatSpecPow) ? 1 : (kLdsTiles && 
                     // first, so the longest chains start in the first round (coop: shared by the
                     // workgroup in builds that keep the cooperative paths, render_sub)
                     // (the first sub-block's rays by value: a pointer would keep them in scratch memory)
-                    render_sub<kCull, kLdsTiles, kMat, kDense>(p, fo, cam, rm, sc, (uint32_t)sx * kSubW, (uint32_t)sy * kBlkH,
-                                                       active, s_hot, s_cull, s_bins, s_rgb, s_ppm, aligned,
-                                                       kGivenRay && r == 0, d0, coop, pre, pobj, mid);
+                    render_sub<kCull, kLdsTiles, kMat, kDense, kOne>(p, fo, cam, rm, sc, (uint32_t)sx * kSubW,
+                                                             (uint32_t)sy * kBlkH, active, s_hot, s_cull, s_bins, s_rgb,
+                                                             s_ppm, aligned, kGivenRay && r == 0, d0, coop, pre, pobj,
+                                                             mid, h_counts);
                 }
             };
             if constexpr (kLdsScene) {
@@ -1923,7 +1947,7 @@ hipError_t launch_k(void (*kernel)(KArgs...), uint32_t grid, size_t dyn, hipStre
     return hipGetLastError();
 }
 
-template <bool C, bool L, int M, bool K, bool D = false, bool V = false>
+template <bool C, bool L, int M, bool K, bool D = false, bool V = false, bool O = false>
 hipError_t launch_frame_kernel(const FrameParams& p, uint32_t want, size_t dyn, const LaunchCtx& lc, hipStream_t s) {
     static std::mutex mu;  // resident workgroups per CU of this build, per dynamic LDS size
     static int per_cu = -1;
@@ -1932,7 +1956,7 @@ hipError_t launch_frame_kernel(const FrameParams& p, uint32_t want, size_t dyn, 
     {
         std::lock_guard<std::mutex> lock(mu);
         if (per_cu < 0 || per_cu_dyn != dyn) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, frame_kernel<C, L, M, K, D, V>, kWG, dyn) !=
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, frame_kernel<C, L, M, K, D, V, O>, kWG, dyn) !=
                     hipSuccess ||
                 per_cu <= 0)
                 per_cu = 1;
@@ -2007,7 +2031,7 @@ hipError_t launch_frame_kernel(const FrameParams& p, uint32_t want, size_t dyn, 
             hipError_t e;
             if ((e = hipEventRecord(lc.fork, s)) != hipSuccess || (e = hipStreamWaitEvent(lc.side, lc.fork, 0)) != hipSuccess)
                 return e;
-            if ((e = launch_k(frame_kernel<C, L, M, K, D, V>, dgrid, dyn, s, lc.frame_t, q.objects, q.lights, q.cull,
+            if ((e = launch_k(frame_kernel<C, L, M, K, D, V, O>, dgrid, dyn, s, lc.frame_t, q.objects, q.lights, q.cull,
                               q.tris, aux_arg<K>(q), q.nobj | (q.nlights << 16), q.total_tris, q.total_sub,
                               frame_roles(dgrid, q), band_word(q), q)) != hipSuccess)
                 return e;
@@ -2017,7 +2041,7 @@ hipError_t launch_frame_kernel(const FrameParams& p, uint32_t want, size_t dyn, 
             return hipStreamWaitEvent(s, lc.join, 0);
         }
     }
-    return launch_k(frame_kernel<C, L, M, K, D, V>, grid, dyn, s, lc.frame_t, q.objects, q.lights, q.cull, q.tris,
+    return launch_k(frame_kernel<C, L, M, K, D, V, O>, grid, dyn, s, lc.frame_t, q.objects, q.lights, q.cull, q.tris,
                     aux_arg<K>(q), q.nobj | (q.nlights << 16), q.total_tris, q.total_sub, frame_roles(grid, q), band_word(q),
                     q);
 }
@@ -2028,6 +2052,15 @@ hipError_t launch_frame_cs(const FrameParams& p, uint32_t want, const LaunchCtx&
     // everything is read from the device arrays
     if (p.lds_scene) {
         const size_t dyn = scene_lds_layout(p.nobj, p.nlights, p.total_tris, C).bytes;
+        // one object (main.rs's own scene shape): the single-object path (culled builds; the
+        // brute-force diagnostic keeps the general code) — C2 8 frames 39.6 -> 37.0 us per launch,
+        // one frame alone 9.35 -> 8.62 us; not into a ring beyond the Infinity Cache, where the
+        // unpaced fill bounds the launch and the shorter detail chains beside it measured 0.6 us
+        // slower (C2 in 16 slots 50.3 -> 50.9 us), same-box A/B profiles/r07/ab/
+        if constexpr (C) {
+            if (p.nobj == 1 && !(p.launch_flags & kLaunchRingBeyondCache))
+                return launch_frame_kernel<C, false, M, true, false, V, true>(p, want, dyn, lc, s);
+        }
         return launch_frame_kernel<C, false, M, true, false, V>(p, want, dyn, lc, s);
     }
     if (p.max_object_tris > kDirectMax) {
