@@ -159,5 +159,48 @@ bool build_object(const Hot* faces, uint32_t T, uint32_t node_base, uint32_t slo
     return true;
 }
 
+bool fits_tree_layout(const Built& b, uint32_t faces) {
+    const TreeLayout t = tree_layout(faces - b.unculled);
+    return b.nodes.size() == t.nodes && b.depth == t.depth;
+}
+
+bool build_scene(const Hot* faces, const uint32_t* sizes, size_t nobj, uint32_t min_faces, bool refittable, SceneBuilt* out,
+                 size_t* bad_object, const char** why) {
+    *out = SceneBuilt{};
+    out->objs.resize(nobj);
+    if (nobj) std::memset(out->objs.data(), 0, sizeof(Object) * nobj);
+    uint32_t begin = 0, blocks = 0, culled = 0;
+    for (size_t i = 0; i < nobj; begin += sizes[i], ++i) {
+        const uint32_t n = sizes[i];
+        if (n < min_faces) continue;
+        Built b;
+        *bad_object = i;
+        *why = "too many nodes";
+        if (out->nodes.size() + 2 * (size_t)n > 0x7fffffffu || out->hot.size() + n > 0x7fffffffu) return false;
+        const uint32_t node_base = (uint32_t)out->nodes.size(), slot_base = (uint32_t)out->hot.size();
+        if (!build_object(faces + begin, n, node_base, slot_base, kStackDepth, &b, why)) return false;
+        if (refittable) {
+            *why = "the tree is not the shape its face count lays out";
+            if (!fits_tree_layout(b, n)) return false;
+            const uint32_t C = n - b.unculled;
+            const TreeLayout t = tree_layout(C);
+            out->layout.push_back(gpu::AccelDevLayout{begin, n, slot_base, blocks, (uint32_t)i, C, b.unculled, culled, node_base, t.full,
+                                                      t.extra, 1u});
+            blocks += (n + 255u) / 256u;  // (accel_dev.hip's workgroups of 256 faces)
+            culled += C;
+        }
+        out->objs[i] = b.obj;
+        out->nodes.insert(out->nodes.end(), b.nodes.begin(), b.nodes.end());
+        out->hot.insert(out->hot.end(), b.hot.begin(), b.hot.end());
+        out->index.insert(out->index.end(), b.index.begin(), b.index.end());
+        ++out->objects;
+        out->max_depth = std::max(out->max_depth, b.depth);
+        out->faces += n;
+        out->unculled += b.unculled;
+    }
+    *why = "";
+    return true;
+}
+
 }  // namespace accel
 }  // namespace eray

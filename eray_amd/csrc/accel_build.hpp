@@ -63,6 +63,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "accel_layout.hpp"
 #include "accel_margin.hpp"
 #include "accel_walk.hpp"
 
@@ -86,6 +87,29 @@ struct Built {
 // would be deeper than max_depth.
 bool build_object(const Hot* faces, uint32_t T, uint32_t node_base, uint32_t slot_base, uint32_t max_depth, Built* out,
                   const char** why);
+
+// Is b (build_object's result for `faces` faces) the tree that accel_layout.hpp lays out for its
+// culled count?  The refit's kernels take every node id and range from tree_layout(C): only such a
+// tree may get an AccelDevLayout.
+bool fits_tree_layout(const Built& b, uint32_t faces);
+
+// A scene's hierarchy: what eray_scene_build_ray_accel uploads and reports.
+struct SceneBuilt {
+    std::vector<Object> objs;      // one per object of the scene, zero for those below min_faces
+    std::vector<Node> nodes;       // the covered objects' arrays, concatenated in scene order
+    std::vector<Hot> hot;
+    std::vector<uint32_t> index;
+    std::vector<gpu::AccelDevLayout> layout;  // per covered object, when refittable (numbering 1)
+    uint32_t objects = 0, max_depth = 0;      // covered objects; levels of the deepest tree
+    uint64_t faces = 0, unculled = 0;         // faces of the covered objects; those in unculled lists
+};
+
+// build_object for every object of at least min_faces faces of a scene: `faces` holds the objects'
+// records one after another, sizes[i] of object i.  False, with the object and *why, when the scene
+// would pass 0x7fffffff slots or nodes, a tree would be deeper than kStackDepth or, for refittable,
+// a tree is not fits_tree_layout's.
+bool build_scene(const Hot* faces, const uint32_t* sizes, size_t nobj, uint32_t min_faces, bool refittable, SceneBuilt* out,
+                 size_t* bad_object, const char** why);
 
 }  // namespace accel
 }  // namespace eray

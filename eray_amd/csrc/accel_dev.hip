@@ -45,12 +45,15 @@ namespace {
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kWaves = kBlock / 64;
 
-using DevObj = AccelDevLayout;  // 48 B (owners.hpp: RayAccel keeps the build's for the refit)
+using DevObj = AccelDevLayout;  // 48 B (accel_layout.hpp; RayAccel keeps the build's for the refit)
 static_assert(sizeof(DevObj) == 48, "uploaded as it stands");
 
-struct DevAcc {  // 64 B; lo starts at all ones, the rest at zero
+struct DevAcc {  // 64 B
     unsigned long long lo[3], hi[3], gamma, pad;
 };
+// Before a margin pass: lo at all ones, the rest at zero.  (refit_reset_kernel keeps the literal:
+// through this function its code comes out different.)
+ERAY_HD DevAcc dev_acc_start() { return DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0}; }
 
 struct DevCount {  // the block the host reads back
     uint32_t culled, unculled, status, pad;
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(kBlock) void object_kernel(const DevObj* __restrict
 __global__ __launch_bounds__(kBlock) void refit_reset_kernel(DevAcc* __restrict__ acc, DevCount* __restrict__ cnt, uint32_t nobj) {
     const uint32_t o = blockIdx.x * kBlock + threadIdx.x;
     if (o >= nobj) return;
-    acc[o] = DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0};
+    acc[o] = DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0};  // (dev_acc_start's value)
     cnt[o] = DevCount{0, 0, 0, 0};
 }
 
@@ -379,6 +382,53 @@ struct Arena {
 // The numbering of a layout's trees (one build call made them all): recursion order or level order.
 bool preorder(const std::vector<DevObj>& objs) { return !objs.empty() && objs.front().numbering == 1u; }
 
+// Levels [first, depth) of every covered object's tree by `pass` (a level kernel: level, obj0, then
+// args), deepest first, the objects in chunks of at most 65,535 per grid.y.
+template <typename... Params, typename... Args>
+hipError_t launch_levels(void (*pass)(uint32_t, uint32_t, Params...), uint32_t first, uint32_t depth, uint32_t ncov, hipStream_t s,
+                         const Args&... args) {
+    for (uint32_t level = depth; level-- > first;) {
+        const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
+        for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
+            pass<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, args...);
+            TRY(hipGetLastError());
+        }
+    }
+    return hipSuccess;
+}
+
+// The workgroups of 256 faces that cover a layout's objects (margin_kernel's grid).
+uint32_t layout_blocks(const std::vector<DevObj>& objs) { return objs.back().block_begin + (objs.back().faces + kBlock - 1) / kBlock; }
+
+// A refit's scratch for a layout: the uploaded layout, the accumulators and counters, per face the
+// flag and (alpha, beta), per node the double bounds (no node without a culled face).
+// reserve_refit_scratch lays it out in an arena — the call's own (accel_refit_device) or the one
+// that becomes the persistent workspace (accel_refit_workspace) — and records the offsets in ws;
+// refit_scratch gives the typed pointers for an allocation at `base`.
+void reserve_refit_scratch(Arena& a, const std::vector<DevObj>& objs, size_t node_count, RefitWorkspace& ws) {
+    const size_t ncov = objs.size(), F = objs.back().gbegin + objs.back().faces;
+    ws.o_objs = a.reserve(sizeof(DevObj) * ncov);
+    ws.o_acc = a.reserve(sizeof(DevAcc) * ncov);
+    ws.o_cnt = a.reserve(sizeof(DevCount) * ncov);
+    ws.o_flags = a.reserve(4 * F);
+    ws.o_ab = a.reserve(16 * F);
+    ws.o_bounds = a.reserve(sizeof(accel::NodeBounds) * node_count);
+}
+
+struct RefitScratch {
+    DevObj* objs;
+    DevAcc* acc;
+    DevCount* cnt;
+    uint32_t* flags;
+    double* ab;
+    accel::NodeBounds* bounds;
+};
+RefitScratch refit_scratch(const RefitWorkspace& ws, unsigned char* base) {
+    return RefitScratch{reinterpret_cast<DevObj*>(base + ws.o_objs),     reinterpret_cast<DevAcc*>(base + ws.o_acc),
+                        reinterpret_cast<DevCount*>(base + ws.o_cnt),    reinterpret_cast<uint32_t*>(base + ws.o_flags),
+                        reinterpret_cast<double*>(base + ws.o_ab),       reinterpret_cast<accel::NodeBounds*>(base + ws.o_bounds)};
+}
+
 }  // namespace
 
 hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObject>& covered, size_t nobj, RayAccel& ra,
@@ -424,8 +474,7 @@ hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObj
     unsigned long long *d_keys = a.at<unsigned long long>(o_keys), *d_keys2 = a.at<unsigned long long>(o_keys2);
     uint32_t *d_ids = a.at<uint32_t>(o_ids), *d_ids2 = a.at<uint32_t>(o_ids2);
 
-    std::vector<DevAcc> acc0(ncov);
-    for (DevAcc& x : acc0) x = DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0};
+    const std::vector<DevAcc> acc0(ncov, dev_acc_start());
     TRY(hipMemcpyAsync(d_objs, objs.data(), sizeof(DevObj) * ncov, hipMemcpyHostToDevice, s));
     TRY(hipMemcpyAsync(d_acc, acc0.data(), sizeof(DevAcc) * ncov, hipMemcpyHostToDevice, s));
     TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCount) * ncov, s));
@@ -494,14 +543,7 @@ hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObj
             TRY(rocprim::radix_sort_pairs(b.at<void>(o_sort), sort2_temp, d_flags, d_scan, d_ids2, d_ids, (size_t)P, 0u, ord_bits, s));
             sorted = d_ids;
         }
-        for (uint32_t level = depth; level-- > 0;) {
-            const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
-            for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
-                level_kernel<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, sorted, d_ab, ra.nodes,
-                                                                                       d_bounds, ra.hot, ra.index);
-                TRY(hipGetLastError());
-            }
-        }
+        TRY(launch_levels(level_kernel, 0u, depth, ncov, s, d_hot, d_objs, sorted, d_ab, ra.nodes, d_bounds, ra.hot, ra.index));
         object_kernel<<<(ncov + kBlock - 1) / kBlock, kBlock, 0, s>>>(d_objs, ncov, d_acc, ra.objs);
         TRY(hipGetLastError());
         TRY(hipStreamSynchronize(s));  // (the temporaries go out of scope)
@@ -522,36 +564,26 @@ hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, 
     const std::vector<DevObj>& objs = ra.layout;
     const uint32_t ncov = (uint32_t)objs.size();
     if (!ncov) return hipSuccess;
-    const uint32_t F = objs.back().gbegin + objs.back().faces,
-                   blocks = objs.back().block_begin + (objs.back().faces + kBlock - 1) / kBlock;
-    uint64_t P = 0;
-    for (const DevObj& ob : objs) P += ob.C;
-
+    const uint32_t blocks = layout_blocks(objs);
     Arena a;
-    const size_t o_objs = a.reserve(sizeof(DevObj) * ncov), o_acc = a.reserve(sizeof(DevAcc) * ncov),
-                 o_cnt = a.reserve(sizeof(DevCount) * ncov), o_flags = a.reserve(4 * (size_t)F), o_ab = a.reserve(16 * (size_t)F),
-                 o_bounds = a.reserve(P ? sizeof(accel::NodeBounds) * ra.node_count : 0);
+    RefitWorkspace at;  // (the offsets only: the arena keeps the memory)
+    reserve_refit_scratch(a, objs, ra.node_count, at);
     TRY(a.alloc());
-    DevObj* d_objs = a.at<DevObj>(o_objs);
-    DevAcc* d_acc = a.at<DevAcc>(o_acc);
-    DevCount* d_cnt = a.at<DevCount>(o_cnt);
-    uint32_t* d_flags = a.at<uint32_t>(o_flags);
-    double* d_ab = a.at<double>(o_ab);
+    const RefitScratch w = refit_scratch(at, a.mem);
 
-    std::vector<DevAcc> acc0(ncov);
-    for (DevAcc& x : acc0) x = DevAcc{{~0ull, ~0ull, ~0ull}, {0, 0, 0}, 0, 0};
-    TRY(hipMemcpyAsync(d_objs, objs.data(), sizeof(DevObj) * ncov, hipMemcpyHostToDevice, s));
-    TRY(hipMemcpyAsync(d_acc, acc0.data(), sizeof(DevAcc) * ncov, hipMemcpyHostToDevice, s));
-    TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCount) * ncov, s));
+    const std::vector<DevAcc> acc0(ncov, dev_acc_start());
+    TRY(hipMemcpyAsync(w.objs, objs.data(), sizeof(DevObj) * ncov, hipMemcpyHostToDevice, s));
+    TRY(hipMemcpyAsync(w.acc, acc0.data(), sizeof(DevAcc) * ncov, hipMemcpyHostToDevice, s));
+    TRY(hipMemsetAsync(w.cnt, 0, sizeof(DevCount) * ncov, s));
     if (blocks) {
-        margin_kernel<<<blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, reinterpret_cast<double2*>(d_ab), d_acc, d_cnt);
+        margin_kernel<<<blocks, kBlock, 0, s>>>(d_hot, w.objs, ncov, w.flags, reinterpret_cast<double2*>(w.ab), w.acc, w.cnt);
         TRY(hipGetLastError());
-        refit_check_kernel<<<blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, ra.index, ra.hot, d_cnt);
+        refit_check_kernel<<<blocks, kBlock, 0, s>>>(d_hot, w.objs, ncov, w.flags, ra.index, ra.hot, w.cnt);
         TRY(hipGetLastError());
     }
     // the one round trip, the build's: 16 B of counters per covered object
     std::vector<DevCount> cnt(ncov);
-    TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(DevCount) * ncov, hipMemcpyDeviceToHost, s));
+    TRY(hipMemcpyAsync(cnt.data(), w.cnt, sizeof(DevCount) * ncov, hipMemcpyDeviceToHost, s));
     TRY(hipStreamSynchronize(s));
     for (uint32_t i = 0; i < ncov; ++i) {
         if (cnt[i].status || cnt[i].culled != objs[i].C || cnt[i].unculled != objs[i].U) return hipSuccess;  // a class change
@@ -559,19 +591,10 @@ hipError_t accel_refit_device(const TriHot* d_hot, RayAccel& ra, hipStream_t s, 
     }
     info->nodes = ra.node_count;
     info->max_depth = ra.max_depth;
-    if (P) {
-        accel::NodeBounds* d_bounds = a.at<accel::NodeBounds>(o_bounds);
-        const auto level_pass = preorder(objs) ? refit_level_preorder_kernel : refit_level_kernel;
-        for (uint32_t level = ra.max_depth; level-- > 0;) {
-            const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
-            for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
-                level_pass<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes, d_bounds,
-                                                                                     ra.hot, ra.index);
-                TRY(hipGetLastError());
-            }
-        }
-    }
-    object_kernel<<<(ncov + kBlock - 1) / kBlock, kBlock, 0, s>>>(d_objs, ncov, d_acc, ra.objs);
+    if (ra.node_count)
+        TRY(launch_levels(preorder(objs) ? refit_level_preorder_kernel : refit_level_kernel, 0u, ra.max_depth, ncov, s, d_hot, w.objs,
+                          w.ab, ra.nodes, w.bounds, ra.hot, ra.index));
+    object_kernel<<<(ncov + kBlock - 1) / kBlock, kBlock, 0, s>>>(w.objs, ncov, w.acc, ra.objs);
     TRY(hipGetLastError());
     TRY(hipStreamSynchronize(s));  // (the temporaries go out of scope)
     *kept = true;
@@ -584,20 +607,11 @@ hipError_t accel_refit_workspace(RayAccel& ra, hipStream_t s) {
     const std::vector<DevObj>& objs = ra.layout;
     const uint32_t ncov = (uint32_t)objs.size();
     if (!ncov) return hipSuccess;
-    const uint32_t F = objs.back().gbegin + objs.back().faces;
-    uint64_t P = 0;
     uint32_t max_full = 0;
-    for (const DevObj& ob : objs) {
-        P += ob.C;
+    for (const DevObj& ob : objs)
         if (ob.C) max_full = std::max(max_full, ob.full);
-    }
     Arena a;
-    ws.o_objs = a.reserve(sizeof(DevObj) * ncov);
-    ws.o_acc = a.reserve(sizeof(DevAcc) * ncov);
-    ws.o_cnt = a.reserve(sizeof(DevCount) * ncov);
-    ws.o_flags = a.reserve(4 * (size_t)F);
-    ws.o_ab = a.reserve(16 * (size_t)F);
-    ws.o_bounds = a.reserve(P ? sizeof(accel::NodeBounds) * ra.node_count : 0);
+    reserve_refit_scratch(a, objs, ra.node_count, ws);
     ws.o_verdict = a.reserve(4 * (size_t)ncov);
     ws.o_refits = a.reserve(4);
     TRY(a.alloc());
@@ -609,7 +623,7 @@ hipError_t accel_refit_workspace(RayAccel& ra, hipStream_t s) {
     TRY(hipStreamSynchronize(s));  // (the uploads' sources are this call's)
     ws.bytes = std::max<size_t>(a.need, 256);
     ws.ncov = ncov;
-    ws.blocks = objs.back().block_begin + (objs.back().faces + kBlock - 1) / kBlock;
+    ws.blocks = layout_blocks(objs);
     ws.first_deep = accel::refit_first_deep(max_full);
     ws.mem = std::move(a.mem);
     return hipSuccess;
@@ -624,48 +638,36 @@ hipError_t accel_refit_workspace(RayAccel& ra, hipStream_t s) {
 // — and stores to slots and node ids computed from the layout; make_inner reads two node ids computed
 // from the layout.  No face value (NaN, infinite, huge) reaches an index: such values end in boxes
 // and margins of an object whose record then says has = 0.  A host-built tree qualifies on the same
-// terms: capi.cpp records its layout only after checking that its node count and depth are
-// tree_layout(C)'s.
+// terms: accel_build.cpp's build_scene records its layout only after checking that its node count and
+// depth are tree_layout(C)'s (fits_tree_layout).
 hipError_t accel_refit_enqueue(const TriHot* d_hot, RayAccel& ra, hipStream_t s) {
     const RefitWorkspace& ws = ra.refit;
     const uint32_t ncov = ws.ncov;
     if (!ws.ready() || !ncov) return hipSuccess;
     unsigned char* base = ws.mem;
-    DevObj* d_objs = reinterpret_cast<DevObj*>(base + ws.o_objs);
-    DevAcc* d_acc = reinterpret_cast<DevAcc*>(base + ws.o_acc);
-    DevCount* d_cnt = reinterpret_cast<DevCount*>(base + ws.o_cnt);
-    uint32_t* d_flags = reinterpret_cast<uint32_t*>(base + ws.o_flags);
-    double* d_ab = reinterpret_cast<double*>(base + ws.o_ab);
-    accel::NodeBounds* d_bounds = reinterpret_cast<accel::NodeBounds*>(base + ws.o_bounds);
+    const RefitScratch w = refit_scratch(ws, base);
     const uint32_t og = (ncov + kBlock - 1) / kBlock;
-    refit_reset_kernel<<<og, kBlock, 0, s>>>(d_acc, d_cnt, ncov);
+    refit_reset_kernel<<<og, kBlock, 0, s>>>(w.acc, w.cnt, ncov);
     TRY(hipGetLastError());
     if (ws.blocks) {
-        margin_kernel<<<ws.blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, reinterpret_cast<double2*>(d_ab), d_acc, d_cnt);
+        margin_kernel<<<ws.blocks, kBlock, 0, s>>>(d_hot, w.objs, ncov, w.flags, reinterpret_cast<double2*>(w.ab), w.acc, w.cnt);
         TRY(hipGetLastError());
-        refit_check_kernel<<<ws.blocks, kBlock, 0, s>>>(d_hot, d_objs, ncov, d_flags, ra.index, ra.hot, d_cnt);
+        refit_check_kernel<<<ws.blocks, kBlock, 0, s>>>(d_hot, w.objs, ncov, w.flags, ra.index, ra.hot, w.cnt);
         TRY(hipGetLastError());
     }
     if (ra.node_count) {
         const uint32_t first_deep = ra.refit_top_levels ? ws.first_deep : 0u;
         const bool pre = preorder(ra.layout);
-        const auto level_pass = pre ? refit_level_preorder_kernel : refit_level_kernel;
         const auto top_pass = pre ? refit_top_levels_preorder_kernel : refit_top_levels_kernel;
-        for (uint32_t level = ra.max_depth; level-- > first_deep;) {
-            const uint32_t gx = (uint32_t)(((1ull << level) + kBlock - 1) / kBlock);
-            for (uint32_t o0 = 0; o0 < ncov; o0 += 65535u) {
-                level_pass<<<dim3(gx, std::min(ncov - o0, 65535u)), kBlock, 0, s>>>(level, o0, d_hot, d_objs, d_ab, ra.nodes, d_bounds,
-                                                                                     ra.hot, ra.index);
-                TRY(hipGetLastError());
-            }
-        }
+        TRY(launch_levels(pre ? refit_level_preorder_kernel : refit_level_kernel, first_deep, ra.max_depth, ncov, s, d_hot, w.objs, w.ab,
+                          ra.nodes, w.bounds, ra.hot, ra.index));
         if (first_deep) {
-            top_pass<<<ncov, kBlock, 0, s>>>(std::min(first_deep, ra.max_depth), 0u, d_hot, d_objs, d_ab, ra.nodes, d_bounds, ra.hot,
+            top_pass<<<ncov, kBlock, 0, s>>>(std::min(first_deep, ra.max_depth), 0u, d_hot, w.objs, w.ab, ra.nodes, w.bounds, ra.hot,
                                              ra.index);
             TRY(hipGetLastError());
         }
     }
-    refit_object_kernel<<<og, kBlock, 0, s>>>(d_objs, ncov, d_acc, d_cnt, ra.objs, reinterpret_cast<uint32_t*>(base + ws.o_verdict),
+    refit_object_kernel<<<og, kBlock, 0, s>>>(w.objs, ncov, w.acc, w.cnt, ra.objs, reinterpret_cast<uint32_t*>(base + ws.o_verdict),
                                               reinterpret_cast<uint32_t*>(base + ws.o_refits));
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 // accel_dev.hpp — the device-side builder of the ray-query hierarchy (accel_dev.hip): the same
 // records as accel_build.hpp's host builder (accel_walk.hpp Object / Node, leaf-ordered TriHot
 // copies, the index array), built on a stream from the resident face records.  Host interface
-// only; capi.cpp's eray_scene_build_ray_accel_device owns the context side.
+// only; capi_rays.cpp's eray_scene_build_ray_accel_device owns the context side.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,8 +34,8 @@ struct AccelDevInfo {
 hipError_t accel_build_device(const TriHot* d_hot, const std::vector<AccelDevObject>& covered, size_t nobj, RayAccel& ra,
                               hipStream_t s, AccelDevInfo* info, const char** refuse);
 
-// Refits a hierarchy that accel_build_device built, or a host build whose layout capi.cpp recorded
-// (eray_scene_build_ray_accel_refittable: numbering 1) (ra.layout, ra.max_depth, its four arrays) to
+// Refits a hierarchy that accel_build_device built, or a host build whose layout build_scene recorded
+// (accel_build.hpp; eray_scene_build_ray_accel_refittable: numbering 1) (ra.layout, ra.max_depth, its four arrays) to
 // the records d_hot now holds, on stream s, and waits for it: the topology, the slots and the
 // unculled lists stay; every margin, box, min_index, record copy and gamma is recomputed by the
 // build's functions.  The same one device-to-host copy as the build.  *kept is false (ra's arrays

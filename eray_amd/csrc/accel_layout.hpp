@@ -23,6 +23,21 @@
 #include "accel_walk.hpp"
 
 namespace eray {
+namespace gpu {
+
+// A covered object as the device builder laid it out (accel_dev.hip; 48 B, uploaded as it stands).
+// The refittable host build (accel_build.hpp build_scene) derives the same record from its results;
+// cbase is the build's alone.  numbering: how the tree's nodes are numbered — 0 level by level (the
+// device build), 1 in recursion order (the host build); one value per scene.
+struct AccelDevLayout {
+    uint32_t hot_begin, faces, gbegin, block_begin;
+    uint32_t index, C, U, cbase;                 // C, U, cbase: the culled / unculled counts, first sorted position
+    uint32_t node_base, full, extra, numbering;  // (TreeLayout, LevelOrder / PreOrder below)
+};
+static_assert(sizeof(AccelDevLayout) == 48, "the kernels' record");
+
+}  // namespace gpu
+
 namespace accel {
 
 // 21 bits of v spread to every third bit

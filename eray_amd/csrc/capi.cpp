@@ -1,5 +1,6 @@
-// capi.cpp — implementation of include/eray_hip.h: context, device memory, scene upload and
-// kernel launches.  Host code only; the kernels live in render.hip and shaderlib.hip.
+// capi.cpp — implementation of include/eray_hip.h: context, device memory, scene upload and the
+// frame path's kernel launches (the ray queries and their hierarchy: capi_rays.cpp, on the same
+// context, ctx.hpp).  Host code only; the kernels live in render.hip and shaderlib.hip.
 //
 // Error policy: every HIP call is checked; failures and every case where the reference would
 // panic become a status code plus a message (eray_last_error).  Nothing here falls back to a
@@ -7,7 +8,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,38 +18,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/eray_hip.h"
-#include "accel_build.hpp"
-#include "accel_check.hpp"
-#include "accel_dev.hpp"
-#include "accel_layout.hpp"
-#include "internal.hpp"
-#include "owners.hpp"
+#include "ctx.hpp"
 #include "rays_args.hpp"
-
-using namespace eray::gpu;
 
 namespace {
 thread_local std::string g_thread_error;
 constexpr size_t kMaxTags = 512;
-constexpr uint32_t kUnionRing = 4;  // camera paths whose rectangle unions the host keeps
-
-struct HostObject {
-    std::vector<float> raw;  // T*9 positions | T*9 normals | T*6 uvs
-    uint32_t T = 0;
-    // eray_scene_update_object replaced (part of) the geometry from device arrays: the resident raw
-    // array holds it, `raw` does not (refresh_raw reads it back before the scene is uploaded again)
-    bool raw_stale = false;
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    eray_material mat{};
-    bool example = false;  // color + diffuse from main.rs's graph at the hit texel
-    eray_material_example_params ex{};
-    std::vector<eray_texel_node> tnodes;  // a shader graph per hit texel (texel_graph)
-    int32_t tout[5] = {-1, -1, -1, -1, -1};
-};
-
-// Node types of the shaderlib outputs: wave's is IValue, rgb / flat_color / mix_color's IColor.
-bool texel_is_color(uint32_t kind) { return kind != ERAY_TEXEL_WAVE; }
 
 // Expands node `idx` of `nodes` (evaluated at a texel derived from instruction `parent` by
 // `xform`) into pre-order instructions; indices are relative to `first`.
@@ -85,143 +59,7 @@ uint32_t texel_emit(const std::vector<eray_texel_node>& nodes, uint32_t idx, uin
 }
 }  // namespace
 
-struct eray_ctx {
-    int device = 0;
-    Stream own_stream;
-    hipStream_t stream = nullptr;  // own_stream, or the caller's (eray_set_stream)
-    std::string err;
-
-    eray_camera camera{{0.0f, 0.0f, 0.0f}, {60.0f, 60.0f}, 1024u, 1.0f};  // Camera::default()
-    std::vector<eray_light> lights;
-    std::vector<HostObject> objects;
-
-    bool geom_dirty = true, desc_dirty = true;
-    uint64_t scene_gen = 0;  // bumped whenever geometry or descriptors are uploaded
-    DeviceBuf<TriHot> d_hot;
-    DeviceBuf<TriShade> d_shade;
-    DeviceBuf<TriCull> d_cull;
-    DeviceBuf<TriCull> d_tcull;  // kTraceSkipTris records: trace.hip's background skip
-    DeviceBuf<float> d_raw;
-    DeviceBuf<ObjectDesc> d_objs;
-    DeviceBuf<LightDesc> d_lights;
-    RayAccel ray_accel;  // eray_scene_build_ray_accel's hierarchy; invalid after any geometry change
-    // launch plans of eray_render_frames / eray_render_camera_path: HIP graphs of back-to-back
-    // frames (chunks of up to kGraphFrames frames and remainders), each cached for the frame
-    // parameters + stream + length + kind it was captured with; the least recently used is
-    // evicted beyond kGraphCache
-    std::vector<FrameGraph> graphs;
-    uint64_t graph_clock = 0;
-    DeviceBuf<uint32_t> d_prog;  // every object's texel program (MaterialDesc::prog), concatenated
-    std::vector<uint32_t> h_prog;
-    std::vector<ObjectDesc> h_objs;  // kept alive for the async uploads
-    std::vector<LightDesc> h_lights;
-    std::vector<float> h_raw;
-    std::vector<uint32_t> h_begin;   // obj_begin (nobj + 1) | objkey (nobj), uploaded with the descriptors
-    uint32_t total_tris = 0;
-    uint32_t binned = 0;       // objects of more than kDirectMax faces (sync_scene)
-    bool spec_pow = false;     // some material has a specular-power output
-    bool example_mat = false;  // some material is main.rs's graph evaluated per hit
-    // ---- per-camera setup (setup.hip, bins.hip), all on the device
-    DeviceBuf<CamDev> d_cam;      // the context camera's device slot
-    DeviceBuf<CamState> d_state;  // the last setup's results
-    PinnedBuf<CamState> h_state;  // host copy, valid once state_ev has completed
-    Event state_ev;
-    bool state_pending = false;   // a copy into h_state is in flight
-    bool state_known = false;     // h_state holds the results of the setup of setup_key
-    std::vector<uint64_t> setup_key;  // camera, size, rows and scene generation of the last setup
-    std::vector<uint64_t> tcull_key;  // camera, size, scene generation and stream of d_tcull's records
-    FrameSource setup_src;        // the last enqueued scene-camera setup: its source key and rows
-    PinnedBuf<ObjectDesc> h_objs_state;  // the descriptors after that setup (pixel rectangles)
-    // where the frames in output buffers came from (eray_gather_frames): PPM slot address -> the
-    // source of the last render enqueued into it, most recent last (at most kMaxTags)
-    struct SlotTag {
-        uintptr_t ppm;
-        FrameSource src;
-    };
-    std::vector<SlotTag> slot_tags;
-    // camera paths: call counter (kSrcPath keys) and the union of every path camera's object
-    // rectangles — accumulated on the device (d_union_acc, captured into path graphs), then copied
-    // into ring entry seq % kUnionRing on the device and the host, with an event per entry
-    uint64_t path_seq = 0;
-    DeviceBuf<int32_t> d_union_acc;
-    size_t union_cap() const { return d_union_acc.cap / 4; }  // objects per entry
-    PinnedBuf<int32_t> h_union;  // mapped: the flush kernel writes it through h_union.dev
-    uint64_t union_seq[kUnionRing] = {};
-    FrameSource union_src[kUnionRing];
-    uint32_t union_nobj[kUnionRing] = {};  // objects and scene generation the entry's union covers
-    uint64_t union_gen[kUnionRing] = {};
-    Event union_ev[kUnionRing];
-    // eray_gather_frames' plan (comm.cpp owns it)
-    void* gather_plan = nullptr;
-    void (*gather_plan_free)(void*) = nullptr;
-    DeviceBuf<uint32_t> d_acc;    // setup counter, partials and rectangle accumulators (enqueue_setup)
-    DeviceBuf<uint32_t> d_begin;  // obj_begin | objkey
-    DeviceBuf<int4> d_range;      // binned faces' bin rectangles, areas, binned-object index
-    DeviceBuf<unsigned long long> d_area;
-    DeviceBuf<uint32_t> d_fkey;
-    BinBuffers bins;              // (bins.hip's own allocation: bins_alloc / bins_free)
-    std::vector<uint64_t> bins_layout;
-    uint64_t bins_gen = 0;        // bumped whenever bins_alloc (re)allocates the bin buffers
-    size_t bin_cap = 0;           // entry capacity to allocate (grown when a setup overflows)
-    bool rect_pairs = false;      // (diagnostics) setups walk the bin rectangles' pairs (bins.hip)
-    // camera paths (eray_render_camera_path): the cameras of the current graph chunk on the
-    // device, the whole path staged in pinned memory
-    DeviceBuf<CamDev> d_path;
-    DeviceBuf<CamDev> d_path_all;
-    // two pinned staging buffers used in turn: a call waits only for the upload two calls back
-    // (not for the previous call's frames, which its upload is queued behind)
-    PinnedBuf<CamDev> h_path[2];
-    Event path_ev[2];  // each buffer's last upload (reusable once complete)
-    uint32_t path_buf = 0;
-    // batched setups of a path chunk's cameras (scenes without binned objects): per camera slot
-    // its culling records, object descriptors and setup state
-    DeviceBuf<TriCull> d_bcull;
-    DeviceBuf<ObjectDesc> d_bobjs;
-    DeviceBuf<CamState> d_bstate;
-    // camera paths of scenes with binned objects: the setups of up to mc_k cameras in one
-    // multi-camera build (SetupParams::ncam), into per-camera slices of a buffer set; two sets, so
-    // that the next cameras' build (on mc_stream) runs beside the current cameras' frames
-    struct MultiSet {
-        DeviceBuf<TriCull> cull;
-        DeviceBuf<ObjectDesc> objs;
-        DeviceBuf<CamState> state;
-        DeviceBuf<uint32_t> acc;
-        DeviceBuf<int4> range;
-        DeviceBuf<unsigned long long> area;
-        DeviceBuf<uint32_t> fkey;
-        BinBuffers bins;
-    };
-    MultiSet mc[2];
-    uint32_t mc_k = 0;
-    std::vector<uint64_t> mc_layout;
-    uint64_t mc_gen = 0;          // bumped whenever the multi-camera buffers are (re)allocated
-    Stream mc_stream;
-    Event mc_fork, mc_ready[2], mc_free[2];
-    // the latest render of the scene camera or of a camera path (tag_frames): what a scene-camera
-    // gather plans for — state every rank holds alike when the ranks make the same render calls
-    FrameSource gather_src;
-    DeviceBuf<uint8_t> d_coll;     // kCollScratchBytes: the gathers' status exchanges (comm.cpp)
-    DeviceBuf<uint8_t> d_staging;  // eray_gather_rows' banded staging (rank 0)
-    // the separate fill's stream and events, and the launchers' view of them
-    Stream fill_stream;
-    Event fill_fork, fill_join;
-    LaunchCtx lc{nullptr, nullptr, nullptr};
-    Event update_join;  // eray_scene_update_object: the other streams' work so far, waited for by `stream`
-
-    // Waits for the context's streams, then releases what the members do not own themselves.
-    ~eray_ctx() {
-        (void)hipSetDevice(device);
-        for (hipStream_t s : {stream, (hipStream_t)own_stream, (hipStream_t)mc_stream})
-            if (s) (void)hipStreamSynchronize(s);
-        if (gather_plan && gather_plan_free) gather_plan_free(gather_plan);  // (while the streams exist)
-        bins_free(bins);
-        for (auto& m : mc) bins_free(m.bins);
-    }
-};
-
-namespace {
-
-int set_error(eray_ctx* ctx, int code, const char* fmt, ...) {
+int eray::gpu::set_error(eray_ctx* ctx, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -234,34 +72,6 @@ int set_error(eray_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return set_error((ctx), e_ == hipErrorOutOfMemory ? ERAY_E_OUT_OF_MEMORY : ERAY_E_HIP, \
-                             "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-int use_device(eray_ctx* ctx) {
-    if (!ctx) return set_error(nullptr, ERAY_E_INVALID_ARGUMENT, "null context");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ERAY_OK;
-}
-
-}  // namespace
-
-// (owners.hpp)
-template <typename T>
-int eray::gpu::DeviceBuf<T>::ensure(eray_ctx* ctx, size_t need) {
-    if (need <= this->cap && this->p_) return ERAY_OK;
-    if (this->p_) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, this->release());
-    }
-    HIP_TRY(ctx, alloc(need ? need : 1));
-    return ERAY_OK;
-}
-
 namespace {
 
 uint32_t sat_u32_host(float f) {
@@ -272,8 +82,9 @@ uint32_t sat_u32_host(float f) {
 
 bool image_ok(const eray_image& im) { return !im.data || (im.width > 0 && im.height > 0); }
 TexView tex(const eray_image& im) { return TexView{im.data, im.width, im.height}; }
+}  // namespace
 
-int sync_scene(eray_ctx* ctx) {
+int eray::gpu::sync_scene(eray_ctx* ctx) {
     int st;
     // The host staging vectors below feed async copies: drain earlier ones before reuse.
     if (ctx->geom_dirty || ctx->desc_dirty) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -426,6 +237,7 @@ int sync_scene(eray_ctx* ctx) {
     return ERAY_OK;
 }
 
+namespace {
 // Brings HostObject::raw up to date for the objects whose geometry eray_scene_update_object took
 // from device arrays (their slices of the resident raw array; synchronises).  Such an object exists
 // only while the geometry is resident: the update uploads the scene first, and every call that
@@ -1191,12 +1003,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     if (!rp) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "params is null");
     // anti-aliasing and reflection bounces take the general tracer (trace.hip); bounces only
     // matter when some material has a reflection output (engine.rs:181-182)
-    bool reflective = false;
-    for (auto& o : ctx->objects) {
-        const int32_t r = o.tout[4];  // a graph output replaces the texture (None if mistyped)
-        reflective |= r >= 0 ? !texel_is_color(o.tnodes[r].kind) : o.mat.reflection.data != nullptr;
-    }
-    const uint32_t bounces = reflective ? rp->bounces : 0u;
+    const uint32_t bounces = scene_reflective(ctx) ? rp->bounces : 0u;
     if (bounces > kMaxBounces)
         return set_error(ctx, ERAY_E_UNSUPPORTED, "bounces = %u: at most %u reflection levels", rp->bounces,
                          kMaxBounces);
@@ -1356,361 +1163,6 @@ int eray_render(eray_ctx* ctx, const eray_render_params* rp) {
         HIP_TRY(ctx, launch_frame(ctx, p));
         tag_frames(ctx, p.out_ppm, 0, 1, render_source(ctx, p, rp));
     }
-    return ERAY_OK;
-}
-
-// Ray queries (rays.hip): the batch's kernel on the context's stream, nothing else — no setup, no
-// copy back, so a call on an uploaded scene can be captured into a graph.
-int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* rp) {
-    if (int st = use_device(ctx)) return st;
-    const char* why = "";
-    if (int st = eray::check_rays_params(rp, ctx->objects.size(), &why)) return set_error(ctx, st, "eray_cast_rays: %s", why);
-    if (!rp->count) return ERAY_OK;
-    if (int st = sync_scene(ctx)) return st;
-    // bounces only matter when some material has a reflection output (engine.rs:181-182)
-    bool reflective = false;
-    for (auto& o : ctx->objects) {
-        const int32_t r = o.tout[4];
-        reflective |= r >= 0 ? !texel_is_color(o.tnodes[r].kind) : o.mat.reflection.data != nullptr;
-    }
-    RayBatch b;
-    std::memset(&b, 0, sizeof b);
-    FrameParams& p = b.f;
-    p.nframes = 1;
-    p.cx = ctx->camera.center[0];
-    p.cy = ctx->camera.center[1];
-    p.cz = ctx->camera.center[2];
-    p.tris = ctx->d_hot;
-    p.shade = ctx->d_shade;
-    p.objects = ctx->d_objs;
-    p.lights = ctx->d_lights;
-    p.nobj = (uint32_t)ctx->objects.size();
-    p.nlights = (uint32_t)ctx->lights.size();
-    p.total_tris = ctx->total_tris;
-    p.bounces = reflective ? rp->bounces : 0u;
-    b.rays = reinterpret_cast<const RayIn*>(rp->rays);
-    b.count = rp->count;
-    b.object = rp->object;
-    b.normalize = (rp->flags & ERAY_RAYS_NORMALIZE) ? 1u : 0u;
-    b.brute = (rp->flags & ERAY_RAYS_BRUTE_FORCE) ? 1u : 0u;
-    b.out_hit = reinterpret_cast<uint4*>(rp->out_hit);
-    b.out_rgb = rp->out_rgb;
-    RayAccelView av{nullptr, nullptr, nullptr, nullptr};
-    if (ctx->ray_accel.valid)  // (never a stale tree: every geometry change clears `valid`)
-        av = RayAccelView{ctx->ray_accel.objs, ctx->ray_accel.nodes,
-                          reinterpret_cast<const TriHot*>((const eray::accel::Hot*)ctx->ray_accel.hot), ctx->ray_accel.index};
-    HIP_TRY(ctx, launch_cast_rays(b, av, ctx->stream));
-    return ERAY_OK;
-}
-
-// Engine::reaches_light for caller-supplied shadow rays (rays.hip reach_kernel): one kernel on the
-// context's stream like eray_cast_rays, so a call on an uploaded scene can be captured.
-int eray_rays_reach_light(eray_ctx* ctx, const eray_reach_params* rp) {
-    if (int st = use_device(ctx)) return st;
-    const char* why = "";
-    if (int st = eray::check_reach_params(rp, &why)) return set_error(ctx, st, "eray_rays_reach_light: %s", why);
-    if (!rp->count) return ERAY_OK;
-    if (int st = sync_scene(ctx)) return st;
-    ReachBatch b;
-    std::memset(&b, 0, sizeof b);
-    FrameParams& p = b.f;
-    p.nframes = 1;
-    p.tris = ctx->d_hot;
-    p.objects = ctx->d_objs;
-    p.nobj = (uint32_t)ctx->objects.size();
-    p.total_tris = ctx->total_tris;
-    b.rays = reinterpret_cast<const RayIn*>(rp->rays);
-    b.targets = rp->targets;
-    b.count = rp->count;
-    b.normalize = (rp->flags & ERAY_RAYS_NORMALIZE) ? 1u : 0u;
-    b.brute = (rp->flags & ERAY_RAYS_BRUTE_FORCE) ? 1u : 0u;
-    b.out = rp->out;
-    RayAccelView av{nullptr, nullptr, nullptr, nullptr};
-    if (ctx->ray_accel.valid)  // (never a stale tree: every geometry change clears `valid`)
-        av = RayAccelView{ctx->ray_accel.objs, ctx->ray_accel.nodes,
-                          reinterpret_cast<const TriHot*>((const eray::accel::Hot*)ctx->ray_accel.hot), ctx->ray_accel.index};
-    HIP_TRY(ctx, launch_reach_light(b, av, ctx->stream));
-    return ERAY_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// The ray-query hierarchy (accel_build.hpp) built on the host from the device's own TriHot records
-// — the bits the kernels test — and uploaded, once the scene is uploaded and the stream idle.
-// refittable: the layout a refit needs is recorded as well (AccelDevLayout per covered object, from
-// the Built results; numbering 1: the host builder's recursion order); the arrays are the same.
-int build_accel_host(eray_ctx* ctx, uint32_t min_faces, std::chrono::steady_clock::time_point t0, eray_ray_accel_info* info,
-                     bool refittable) {
-    const char* const fn = refittable ? "eray_scene_build_ray_accel_refittable" : "eray_scene_build_ray_accel";
-    ctx->ray_accel.drop();
-    if (!min_faces) min_faces = 2 * kRayTile;
-    const uint32_t T = ctx->total_tris;
-    static_assert(sizeof(eray::accel::Hot) == sizeof(TriHot), "the builder reads the kernels' records");
-    std::vector<eray::accel::Hot> hot(T);
-    if (T) HIP_TRY(ctx, hipMemcpy(hot.data(), ctx->d_hot, sizeof(TriHot) * (size_t)T, hipMemcpyDeviceToHost));
-    std::vector<eray::accel::Object> objs(ctx->objects.size());
-    std::vector<eray::accel::Node> nodes;
-    std::vector<eray::accel::Hot> leaf;
-    std::vector<uint32_t> index;
-    eray_ray_accel_info out{};
-    std::vector<AccelDevLayout> layout;
-    uint32_t begin = 0, blocks = 0, culled = 0;
-    for (size_t i = 0; i < ctx->objects.size(); ++i) {
-        const uint32_t n = ctx->objects[i].T;
-        std::memset(&objs[i], 0, sizeof objs[i]);
-        if (n >= min_faces) {
-            eray::accel::Built b;
-            const char* why = "";
-            if (nodes.size() + 2 * (size_t)n > 0x7fffffffu || leaf.size() + n > 0x7fffffffu ||
-                !eray::accel::build_object(hot.data() + begin, n, (uint32_t)nodes.size(), (uint32_t)leaf.size(),
-                                     eray::accel::kStackDepth, &b, &why))
-                return set_error(ctx, ERAY_E_UNSUPPORTED, "%s: object %zu: %s", fn, i, *why ? why : "too many nodes");
-            if (refittable) {
-                // the refit's kernels take every node id and range from this record: it must describe the tree
-                const uint32_t C = n - b.unculled;
-                const eray::accel::TreeLayout t = eray::accel::tree_layout(C);
-                if (b.nodes.size() != t.nodes || b.depth != t.depth)
-                    return set_error(ctx, ERAY_E_UNSUPPORTED, "%s: object %zu: the tree is not the shape its face count lays out", fn, i);
-                layout.push_back(AccelDevLayout{begin, n, (uint32_t)leaf.size(), blocks, (uint32_t)i, C, b.unculled, culled,
-                                                (uint32_t)nodes.size(), t.full, t.extra, 1u});
-                blocks += (n + 255u) / 256u;  // (accel_dev.hip's workgroups of 256 faces)
-                culled += C;
-            }
-            objs[i] = b.obj;
-            nodes.insert(nodes.end(), b.nodes.begin(), b.nodes.end());
-            leaf.insert(leaf.end(), b.hot.begin(), b.hot.end());
-            index.insert(index.end(), b.index.begin(), b.index.end());
-            ++out.objects;
-            out.max_depth = std::max(out.max_depth, b.depth);
-            out.faces += n;
-            out.unculled_faces += b.unculled;
-        }
-        begin += n;
-    }
-    out.nodes = nodes.size();
-    if (out.objects) {
-        RayAccel& ra = ctx->ray_accel;
-        HIP_TRY(ctx, ra.objs.alloc(objs.size()));
-        HIP_TRY(ctx, ra.nodes.alloc(std::max<size_t>(nodes.size(), 1)));
-        HIP_TRY(ctx, ra.hot.alloc(std::max<size_t>(leaf.size(), 1)));
-        HIP_TRY(ctx, ra.index.alloc(std::max<size_t>(index.size(), 1)));
-        HIP_TRY(ctx, hipMemcpy(ra.objs, objs.data(), sizeof(eray::accel::Object) * objs.size(), hipMemcpyHostToDevice));
-        if (!nodes.empty())
-            HIP_TRY(ctx, hipMemcpy(ra.nodes, nodes.data(), sizeof(eray::accel::Node) * nodes.size(), hipMemcpyHostToDevice));
-        if (!leaf.empty()) {
-            HIP_TRY(ctx, hipMemcpy(ra.hot, leaf.data(), sizeof(eray::accel::Hot) * leaf.size(), hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(ra.index, index.data(), 4 * index.size(), hipMemcpyHostToDevice));
-        }
-        out.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
-                           sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
-        ra.min_faces = min_faces;
-        ra.node_count = nodes.size();
-        ra.slot_count = leaf.size();
-        ra.builder = refittable ? RayAccel::kHostRefittable : RayAccel::kHost;
-        if (refittable) {
-            ra.layout = std::move(layout);
-            ra.max_depth = out.max_depth;
-        }
-        ra.valid = true;
-    }
-    out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (info) *info = out;
-    return ERAY_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// The host build (synchronous).  A refit after it rebuilds on the device; the async refit refuses.
-int eray_scene_build_ray_accel(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
-    if (int st = use_device(ctx)) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = sync_scene(ctx)) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
-    return build_accel_host(ctx, min_faces, t0, info, false);
-}
-
-// The same build, the same arrays, with what a refit needs kept beside them: the refit calls then
-// keep this tree's topology as they keep a device build's, and rebuild with this builder.
-int eray_scene_build_ray_accel_refittable(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
-    if (int st = use_device(ctx)) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = sync_scene(ctx)) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
-    return build_accel_host(ctx, min_faces, t0, info, true);
-}
-
-}  // extern "C"
-
-namespace {
-// The objects that get a hierarchy: at least min_faces faces.
-std::vector<AccelDevObject> covered_objects(const eray_ctx* ctx, uint32_t min_faces) {
-    std::vector<AccelDevObject> covered;
-    uint32_t begin = 0;
-    for (size_t i = 0; i < ctx->objects.size(); ++i) {
-        const uint32_t n = ctx->objects[i].T;
-        if (n >= min_faces) covered.push_back(AccelDevObject{(uint32_t)i, begin, n});
-        begin += n;
-    }
-    return covered;
-}
-
-// eray_scene_build_ray_accel_device once the scene is uploaded and the stream idle.
-int build_accel_device(eray_ctx* ctx, uint32_t min_faces, std::chrono::steady_clock::time_point t0, eray_ray_accel_info* info) {
-    RayAccel& ra = ctx->ray_accel;
-    ra.drop();
-    if (!min_faces) min_faces = 2 * kRayTile;
-    const std::vector<AccelDevObject> covered = covered_objects(ctx, min_faces);
-    eray_ray_accel_info out{};
-    for (const AccelDevObject& c : covered) {
-        ++out.objects;
-        out.faces += c.faces;
-    }
-    if (out.objects) {
-        AccelDevInfo dev;
-        const char* refuse = nullptr;
-        HIP_TRY(ctx, accel_build_device(ctx->d_hot, covered, ctx->objects.size(), ra, ctx->stream, &dev, &refuse));
-        if (refuse) return set_error(ctx, ERAY_E_UNSUPPORTED, "eray_scene_build_ray_accel_device: %s", refuse);
-        out.nodes = dev.nodes;
-        out.max_depth = dev.max_depth;
-        out.unculled_faces = dev.unculled;
-        out.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
-                           sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
-        ra.min_faces = min_faces;
-        ra.node_count = dev.nodes;
-        ra.slot_count = out.faces;
-        ra.builder = RayAccel::kDevice;
-        ra.valid = true;
-    }
-    out.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (info) *info = out;
-    return ERAY_OK;
-}
-
-// Can a refit keep the topology?  The last build was the device's or the refittable host build and
-// covered these objects, at these places, with these face counts, and no object was added and the
-// scene not reset since (objs has a record per object of the build's scene: the arrays fit that
-// scene only).
-bool same_layout(const eray_ctx* ctx) {
-    const RayAccel& ra = ctx->ray_accel;
-    bool same = ra.refittable() && !ra.scene_changed && ra.objs.cap == ctx->objects.size();
-    if (same) {
-        const std::vector<AccelDevObject> covered = covered_objects(ctx, ra.min_faces);
-        same = covered.size() == ra.layout.size();
-        for (size_t i = 0; same && i < covered.size(); ++i)
-            same = covered[i].index == ra.layout[i].index && covered[i].hot_begin == ra.layout[i].hot_begin &&
-                   covered[i].faces == ra.layout[i].faces;
-    }
-    return same;
-}
-}  // namespace
-
-extern "C" {
-
-// The same hierarchy built on the context's stream from the resident records (accel_dev.hip): one
-// round trip of 16 B of counters per covered object, no face record leaves the device.
-int eray_scene_build_ray_accel_device(eray_ctx* ctx, uint32_t min_faces, eray_ray_accel_info* info) {
-    if (int st = use_device(ctx)) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = sync_scene(ctx)) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the old buffers)
-    return build_accel_device(ctx, min_faces, t0, info);
-}
-
-// Makes the hierarchy valid for the current records: the device build's topology is kept when only
-// eray_scene_update_object happened since (accel_dev.hip accel_refit_device), else a device build.
-// A refittable host build is treated alike: its topology is kept, else it is built again.
-int eray_scene_refit_ray_accel(eray_ctx* ctx, eray_ray_accel_refit_info* info) {
-    if (int st = use_device(ctx)) return st;
-    const auto t0 = std::chrono::steady_clock::now();
-    RayAccel& ra = ctx->ray_accel;
-    if (ra.builder == RayAccel::kNone)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_scene_refit_ray_accel: the scene has no ray-query hierarchy to refit");
-    if (int st = sync_scene(ctx)) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier queries may still read the arrays)
-    eray_ray_accel_refit_info out{};
-    const bool same = same_layout(ctx), host_refittable = ra.builder == RayAccel::kHostRefittable;
-    bool kept = false;
-    if (same) {
-        AccelDevInfo dev;
-        ra.valid = false;  // (until the refit has gone through)
-        HIP_TRY(ctx, accel_refit_device(ctx->d_hot, ra, ctx->stream, &dev, &kept));
-        if (kept) {
-            out.accel.objects = out.refitted = (uint32_t)ra.layout.size();
-            out.accel.max_depth = dev.max_depth;
-            out.accel.nodes = dev.nodes;
-            out.accel.faces = ra.slot_count;
-            out.accel.unculled_faces = dev.unculled;
-            out.accel.device_bytes = sizeof(eray::accel::Object) * ra.objs.cap + sizeof(eray::accel::Node) * ra.nodes.cap +
-                                     sizeof(eray::accel::Hot) * ra.hot.cap + 4 * ra.index.cap;
-            out.accel.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            ra.valid = true;
-        }
-    }
-    if (!kept) {
-        // a caller who chose the host split stays on it (and refittable); every other hierarchy
-        // is replaced by a device build
-        if (int st = host_refittable ? build_accel_host(ctx, ra.min_faces, t0, &out.accel, true)
-                                     : build_accel_device(ctx, ra.min_faces, t0, &out.accel))
-            return st;
-        out.rebuilt = 1;
-    }
-    if (info) *info = out;
-    return ERAY_OK;
-}
-
-// The kept-topology refit enqueued on the context's stream (accel_dev.hip accel_refit_enqueue): the
-// device takes the verdict per covered object and writes it into the object's `has` word, so the
-// host neither waits nor reads; with its workspace in place the call only launches kernels and can
-// be captured.  It never rebuilds: where eray_scene_refit_ray_accel would, it refuses.
-int eray_scene_refit_ray_accel_async(eray_ctx* ctx) {
-    static const char* const fn = "eray_scene_refit_ray_accel_async";
-    if (!ctx) return set_error(nullptr, ERAY_E_INVALID_ARGUMENT, "null context");
-    RayAccel& ra = ctx->ray_accel;
-    if (ra.builder == RayAccel::kNone)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: the scene has no ray-query hierarchy to refit", fn);
-    if (!ra.refittable())
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: the hierarchy was built on the host (only a device build is refitted)", fn);
-    if (!same_layout(ctx))
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                         "%s: the scene's objects are not those of the build (eray_scene_refit_ray_accel rebuilds)", fn);
-    // first of all HIP calls, so that a refusal leaves a capture as it was (the null stream never
-    // captures and is not asked: order_after_side_streams)
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (ctx->stream) HIP_TRY(ctx, hipStreamIsCapturing(ctx->stream, &capturing));
-    if (!ra.refit.ready()) {
-        if (capturing != hipStreamCaptureStatusNone)
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: no workspace yet: call once outside a capture first", fn);
-        if (int st = use_device(ctx)) return st;
-        HIP_TRY(ctx, accel_refit_workspace(ra, ctx->stream));
-    }
-    if (int st = use_device(ctx)) return st;
-    HIP_TRY(ctx, accel_refit_enqueue(ctx->d_hot, ra, ctx->stream));
-    ra.valid = true;  // (per object the device's `has` word carries the truth)
-    return ERAY_OK;
-}
-
-int eray_scene_ray_accel_refit_status(eray_ctx* ctx, eray_ray_accel_refit_status* out) {
-    if (int st = use_device(ctx)) return st;
-    if (!out) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_scene_ray_accel_refit_status: out is null");
-    const RayAccel& ra = ctx->ray_accel;
-    if (!ra.refit.ready())
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                         "eray_scene_ray_accel_refit_status: no refit workspace (eray_scene_refit_ray_accel_async makes it)");
-    eray_ray_accel_refit_status s{};
-    HIP_TRY(ctx, accel_refit_status(ra, ctx->stream, &s.refits, &s.kept));
-    s.covered = ra.refit.ncov;
-    s.fell_back = s.covered - s.kept;
-    s.workspace_bytes = ra.refit.bytes;
-    *out = s;
-    return ERAY_OK;
-}
-
-int eray_scene_drop_ray_accel(eray_ctx* ctx) {
-    if (int st = use_device(ctx)) return st;
-    if (ctx->ray_accel.objs) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (queries in flight read it)
-    ctx->ray_accel.drop();
     return ERAY_OK;
 }
 
@@ -2673,65 +2125,6 @@ extern "C" int eray_debug_set_bin_capacity(eray_ctx* ctx, uint64_t entries) {
     if (!ctx || !entries) return ERAY_E_INVALID_ARGUMENT;
     ctx->bin_cap = std::min((size_t)entries, kMaxBinEntries);
     ctx->setup_key.clear();
-    return ERAY_OK;
-}
-// The current hierarchy (of either builder) and the face records copied back and checked on the
-// host (accel_check.hpp).
-extern "C" int eray_debug_ray_accel_check(eray_ctx* ctx, char* msg, uint32_t cap) {
-    if (int st = use_device(ctx)) return st;
-    if (msg && cap) msg[0] = 0;
-    auto say = [&](int code, const char* text) {
-        if (msg && cap) std::snprintf(msg, cap, "%s", text);
-        return set_error(ctx, code, "eray_debug_ray_accel_check: %s", text);
-    };
-    const RayAccel& ra = ctx->ray_accel;
-    if (!ra.valid) return say(ERAY_E_INVALID_ARGUMENT, "the scene has no ray-query hierarchy");
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t nobj = ctx->objects.size(), T = ctx->total_tris;
-    std::vector<uint32_t> sizes(nobj);
-    for (size_t i = 0; i < nobj; ++i) sizes[i] = ctx->objects[i].T;
-    std::vector<eray::accel::Hot> faces(T), hot(ra.slot_count);
-    std::vector<eray::accel::Object> objs(nobj);
-    std::vector<eray::accel::Node> nodes(ra.node_count);
-    std::vector<uint32_t> index(ra.slot_count);
-    if (T) HIP_TRY(ctx, hipMemcpy(faces.data(), ctx->d_hot, sizeof(TriHot) * T, hipMemcpyDeviceToHost));
-    if (nobj) HIP_TRY(ctx, hipMemcpy(objs.data(), ra.objs, sizeof(eray::accel::Object) * nobj, hipMemcpyDeviceToHost));
-    if (ra.node_count)
-        HIP_TRY(ctx, hipMemcpy(nodes.data(), ra.nodes, sizeof(eray::accel::Node) * ra.node_count, hipMemcpyDeviceToHost));
-    if (ra.slot_count) {
-        HIP_TRY(ctx, hipMemcpy(hot.data(), ra.hot, sizeof(eray::accel::Hot) * ra.slot_count, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(index.data(), ra.index, 4 * ra.slot_count, hipMemcpyDeviceToHost));
-    }
-    const char* bad = eray::accel::check(faces.data(), sizes.data(), nobj, ra.min_faces, objs.data(), nodes.data(), nodes.size(),
-                                         hot.data(), index.data(), index.size());
-    return bad ? say(ERAY_E_BUILD, bad) : ERAY_OK;
-}
-// One of the hierarchy's device arrays as it stands (valid or not, once the stream is idle), so
-// that tests compare whole arrays: which = 0 the Object records, 1 the nodes, 2 the leaf-ordered
-// face records, 3 the index array.  *bytes: its size; copied when out holds that much.
-extern "C" int eray_debug_ray_accel_arrays(eray_ctx* ctx, uint32_t which, void* out, size_t cap, size_t* bytes) {
-    if (int st = use_device(ctx)) return st;
-    const RayAccel& ra = ctx->ray_accel;
-    if (!bytes || which > 3) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_ray_accel_arrays: bad argument");
-    if (ra.builder == RayAccel::kNone)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_ray_accel_arrays: the scene has no ray-query hierarchy");
-    const void* src[4] = {(const eray::accel::Object*)ra.objs, (const eray::accel::Node*)ra.nodes, (const eray::accel::Hot*)ra.hot,
-                          (const uint32_t*)ra.index};
-    const size_t size[4] = {sizeof(eray::accel::Object) * ra.objs.cap, sizeof(eray::accel::Node) * ra.node_count,
-                            sizeof(eray::accel::Hot) * ra.slot_count, 4 * ra.slot_count};
-    *bytes = size[which];
-    if (!out) return ERAY_OK;
-    if (cap < size[which]) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_ray_accel_arrays: out holds %zu of %zu bytes", cap, size[which]);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (size[which]) HIP_TRY(ctx, hipMemcpy(out, src[which], size[which], hipMemcpyDeviceToHost));
-    return ERAY_OK;
-}
-// Diagnostics: whether eray_scene_refit_ray_accel_async runs the levels of at most 256 nodes in one
-// launch (the default) or every level in a launch of its own; the bytes are the same.  Read when the
-// call enqueues: a captured graph keeps the form it was captured with.
-extern "C" int eray_debug_set_refit_top_levels(eray_ctx* ctx, int on) {
-    if (!ctx) return ERAY_E_INVALID_ARGUMENT;
-    ctx->ray_accel.refit_top_levels = on != 0;
     return ERAY_OK;
 }
 

@@ -1,0 +1,227 @@
+// ctx.hpp — the context behind include/eray_hip.h's eray_ctx handle and what the C-ABI translation
+// units (capi.cpp: context, scene, frames; capi_rays.cpp: ray queries and their hierarchy) share to
+// work on it: the error policy (set_error, HIP_TRY, use_device) and the scene upload.  Private to
+// those two files; comm.cpp and objload.cpp reach the context through internal.hpp's eray_internal_*.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/eray_hip.h"
+#include "internal.hpp"
+#include "owners.hpp"
+
+namespace eray {
+namespace gpu {
+
+constexpr uint32_t kUnionRing = 4;  // camera paths whose rectangle unions the host keeps
+
+struct HostObject {
+    std::vector<float> raw;  // T*9 positions | T*9 normals | T*6 uvs
+    uint32_t T = 0;
+    // eray_scene_update_object replaced (part of) the geometry from device arrays: the resident raw
+    // array holds it, `raw` does not (refresh_raw reads it back before the scene is uploaded again)
+    bool raw_stale = false;
+    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    eray_material mat{};
+    bool example = false;  // color + diffuse from main.rs's graph at the hit texel
+    eray_material_example_params ex{};
+    std::vector<eray_texel_node> tnodes;  // a shader graph per hit texel (texel_graph)
+    int32_t tout[5] = {-1, -1, -1, -1, -1};
+};
+
+// Node types of the shaderlib outputs: wave's is IValue, rgb / flat_color / mix_color's IColor.
+inline bool texel_is_color(uint32_t kind) { return kind != ERAY_TEXEL_WAVE; }
+
+}  // namespace gpu
+}  // namespace eray
+
+using namespace eray::gpu;  // (the C-ABI translation units work in it throughout)
+
+struct eray_ctx {
+    int device = 0;
+    Stream own_stream;
+    hipStream_t stream = nullptr;  // own_stream, or the caller's (eray_set_stream)
+    std::string err;
+
+    eray_camera camera{{0.0f, 0.0f, 0.0f}, {60.0f, 60.0f}, 1024u, 1.0f};  // Camera::default()
+    std::vector<eray_light> lights;
+    std::vector<HostObject> objects;
+
+    bool geom_dirty = true, desc_dirty = true;
+    uint64_t scene_gen = 0;  // bumped whenever geometry or descriptors are uploaded
+    DeviceBuf<TriHot> d_hot;
+    DeviceBuf<TriShade> d_shade;
+    DeviceBuf<TriCull> d_cull;
+    DeviceBuf<TriCull> d_tcull;  // kTraceSkipTris records: trace.hip's background skip
+    DeviceBuf<float> d_raw;
+    DeviceBuf<ObjectDesc> d_objs;
+    DeviceBuf<LightDesc> d_lights;
+    RayAccel ray_accel;  // eray_scene_build_ray_accel's hierarchy; invalid after any geometry change
+    // launch plans of eray_render_frames / eray_render_camera_path: HIP graphs of back-to-back
+    // frames (chunks of up to kGraphFrames frames and remainders), each cached for the frame
+    // parameters + stream + length + kind it was captured with; the least recently used is
+    // evicted beyond kGraphCache
+    std::vector<FrameGraph> graphs;
+    uint64_t graph_clock = 0;
+    DeviceBuf<uint32_t> d_prog;  // every object's texel program (MaterialDesc::prog), concatenated
+    std::vector<uint32_t> h_prog;
+    std::vector<ObjectDesc> h_objs;  // kept alive for the async uploads
+    std::vector<LightDesc> h_lights;
+    std::vector<float> h_raw;
+    std::vector<uint32_t> h_begin;   // obj_begin (nobj + 1) | objkey (nobj), uploaded with the descriptors
+    uint32_t total_tris = 0;
+    uint32_t binned = 0;       // objects of more than kDirectMax faces (sync_scene)
+    bool spec_pow = false;     // some material has a specular-power output
+    bool example_mat = false;  // some material is main.rs's graph evaluated per hit
+    // ---- per-camera setup (setup.hip, bins.hip), all on the device
+    DeviceBuf<CamDev> d_cam;      // the context camera's device slot
+    DeviceBuf<CamState> d_state;  // the last setup's results
+    PinnedBuf<CamState> h_state;  // host copy, valid once state_ev has completed
+    Event state_ev;
+    bool state_pending = false;   // a copy into h_state is in flight
+    bool state_known = false;     // h_state holds the results of the setup of setup_key
+    std::vector<uint64_t> setup_key;  // camera, size, rows and scene generation of the last setup
+    std::vector<uint64_t> tcull_key;  // camera, size, scene generation and stream of d_tcull's records
+    FrameSource setup_src;        // the last enqueued scene-camera setup: its source key and rows
+    PinnedBuf<ObjectDesc> h_objs_state;  // the descriptors after that setup (pixel rectangles)
+    // where the frames in output buffers came from (eray_gather_frames): PPM slot address -> the
+    // source of the last render enqueued into it, most recent last (at most kMaxTags)
+    struct SlotTag {
+        uintptr_t ppm;
+        FrameSource src;
+    };
+    std::vector<SlotTag> slot_tags;
+    // camera paths: call counter (kSrcPath keys) and the union of every path camera's object
+    // rectangles — accumulated on the device (d_union_acc, captured into path graphs), then copied
+    // into ring entry seq % kUnionRing on the device and the host, with an event per entry
+    uint64_t path_seq = 0;
+    DeviceBuf<int32_t> d_union_acc;
+    size_t union_cap() const { return d_union_acc.cap / 4; }  // objects per entry
+    PinnedBuf<int32_t> h_union;  // mapped: the flush kernel writes it through h_union.dev
+    uint64_t union_seq[kUnionRing] = {};
+    FrameSource union_src[kUnionRing];
+    uint32_t union_nobj[kUnionRing] = {};  // objects and scene generation the entry's union covers
+    uint64_t union_gen[kUnionRing] = {};
+    Event union_ev[kUnionRing];
+    // eray_gather_frames' plan (comm.cpp owns it)
+    void* gather_plan = nullptr;
+    void (*gather_plan_free)(void*) = nullptr;
+    DeviceBuf<uint32_t> d_acc;    // setup counter, partials and rectangle accumulators (enqueue_setup)
+    DeviceBuf<uint32_t> d_begin;  // obj_begin | objkey
+    DeviceBuf<int4> d_range;      // binned faces' bin rectangles, areas, binned-object index
+    DeviceBuf<unsigned long long> d_area;
+    DeviceBuf<uint32_t> d_fkey;
+    BinBuffers bins;              // (bins.hip's own allocation: bins_alloc / bins_free)
+    std::vector<uint64_t> bins_layout;
+    uint64_t bins_gen = 0;        // bumped whenever bins_alloc (re)allocates the bin buffers
+    size_t bin_cap = 0;           // entry capacity to allocate (grown when a setup overflows)
+    bool rect_pairs = false;      // (diagnostics) setups walk the bin rectangles' pairs (bins.hip)
+    // camera paths (eray_render_camera_path): the cameras of the current graph chunk on the
+    // device, the whole path staged in pinned memory
+    DeviceBuf<CamDev> d_path;
+    DeviceBuf<CamDev> d_path_all;
+    // two pinned staging buffers used in turn: a call waits only for the upload two calls back
+    // (not for the previous call's frames, which its upload is queued behind)
+    PinnedBuf<CamDev> h_path[2];
+    Event path_ev[2];  // each buffer's last upload (reusable once complete)
+    uint32_t path_buf = 0;
+    // batched setups of a path chunk's cameras (scenes without binned objects): per camera slot
+    // its culling records, object descriptors and setup state
+    DeviceBuf<TriCull> d_bcull;
+    DeviceBuf<ObjectDesc> d_bobjs;
+    DeviceBuf<CamState> d_bstate;
+    // camera paths of scenes with binned objects: the setups of up to mc_k cameras in one
+    // multi-camera build (SetupParams::ncam), into per-camera slices of a buffer set; two sets, so
+    // that the next cameras' build (on mc_stream) runs beside the current cameras' frames
+    struct MultiSet {
+        DeviceBuf<TriCull> cull;
+        DeviceBuf<ObjectDesc> objs;
+        DeviceBuf<CamState> state;
+        DeviceBuf<uint32_t> acc;
+        DeviceBuf<int4> range;
+        DeviceBuf<unsigned long long> area;
+        DeviceBuf<uint32_t> fkey;
+        BinBuffers bins;
+    };
+    MultiSet mc[2];
+    uint32_t mc_k = 0;
+    std::vector<uint64_t> mc_layout;
+    uint64_t mc_gen = 0;          // bumped whenever the multi-camera buffers are (re)allocated
+    Stream mc_stream;
+    Event mc_fork, mc_ready[2], mc_free[2];
+    // the latest render of the scene camera or of a camera path (tag_frames): what a scene-camera
+    // gather plans for — state every rank holds alike when the ranks make the same render calls
+    FrameSource gather_src;
+    DeviceBuf<uint8_t> d_coll;     // kCollScratchBytes: the gathers' status exchanges (comm.cpp)
+    DeviceBuf<uint8_t> d_staging;  // eray_gather_rows' banded staging (rank 0)
+    // the separate fill's stream and events, and the launchers' view of them
+    Stream fill_stream;
+    Event fill_fork, fill_join;
+    LaunchCtx lc{nullptr, nullptr, nullptr};
+    Event update_join;  // eray_scene_update_object: the other streams' work so far, waited for by `stream`
+
+    // Waits for the context's streams, then releases what the members do not own themselves.
+    ~eray_ctx() {
+        (void)hipSetDevice(device);
+        for (hipStream_t s : {stream, (hipStream_t)own_stream, (hipStream_t)mc_stream})
+            if (s) (void)hipStreamSynchronize(s);
+        if (gather_plan && gather_plan_free) gather_plan_free(gather_plan);  // (while the streams exist)
+        bins_free(bins);
+        for (auto& m : mc) bins_free(m.bins);
+    }
+};
+
+namespace eray {
+namespace gpu {
+
+// Does some material reflect?  Bounces only matter then (engine.rs:181-182).  A graph output
+// replaces the texture (None if mistyped).
+inline bool scene_reflective(const eray_ctx* ctx) {
+    bool reflective = false;
+    for (auto& o : ctx->objects) {
+        const int32_t r = o.tout[4];
+        reflective |= r >= 0 ? !texel_is_color(o.tnodes[r].kind) : o.mat.reflection.data != nullptr;
+    }
+    return reflective;
+}
+
+// Records the message on the context (without one: for this thread, eray_last_error) and returns
+// `code`.  Defined in capi.cpp, where the thread's message lives.
+int set_error(eray_ctx* ctx, int code, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                   \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return set_error((ctx), e_ == hipErrorOutOfMemory ? ERAY_E_OUT_OF_MEMORY : ERAY_E_HIP, \
+                             "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+inline int use_device(eray_ctx* ctx) {
+    if (!ctx) return set_error(nullptr, ERAY_E_INVALID_ARGUMENT, "null context");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ERAY_OK;
+}
+
+// Uploads what changed of the scene (geometry, descriptors) on the context's stream (capi.cpp).
+int sync_scene(eray_ctx* ctx);
+
+// (owners.hpp)
+template <typename T>
+int DeviceBuf<T>::ensure(eray_ctx* ctx, size_t need) {
+    if (need <= this->cap && this->p_) return ERAY_OK;
+    if (this->p_) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, this->release());
+    }
+    HIP_TRY(ctx, alloc(need ? need : 1));
+    return ERAY_OK;
+}
+
+}  // namespace gpu
+}  // namespace eray

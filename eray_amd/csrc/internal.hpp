@@ -1,4 +1,4 @@
-// internal.hpp — descriptors shared by the C-ABI layer (capi.cpp) and the gfx950 kernels.
+// internal.hpp — descriptors shared by the C-ABI layer (capi.cpp, capi_rays.cpp) and the gfx950 kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 
+#include "accel_layout.hpp"
 #include "accel_walk.hpp"
 
 struct eray_ctx;
@@ -104,25 +105,16 @@ struct DeviceBuf : Buffer<T, hipFree> {
     }
     // At least `need` elements: nothing when they fit, else ctx's stream is synchronised, the old
     // allocation freed and max(need, 1) elements allocated (contents are not kept).  An eray
-    // status; defined in capi.cpp.
+    // status; defined in ctx.hpp.
     int ensure(eray_ctx* ctx, size_t need);
 };
 
-// The scene's ray-query hierarchy on the device (accel_walk.hpp; capi.cpp
+// The scene's ray-query hierarchy on the device (accel_walk.hpp; capi_rays.cpp
 // eray_scene_build_ray_accel and eray_scene_build_ray_accel_device): per object its record, the nodes, the leaf-ordered copies of the
 // face records (TriHot bytes) and their original indices.  `valid` falls with any geometry change
 // (a stale tree is never used; eray_scene_refit_ray_accel makes it valid again); the memory is
-// released by drop() or with the owner.
-// A covered object as the device builder laid it out (accel_dev.hip; 48 B, uploaded as it stands).
-// The refittable host build (capi.cpp) derives the same record from its results; cbase is the
-// build's alone.  numbering: how the tree's nodes are numbered — 0 level by level (the device
-// build), 1 in recursion order (the host build); one value per scene.
-struct AccelDevLayout {
-    uint32_t hot_begin, faces, gbegin, block_begin;
-    uint32_t index, C, U, cbase;                 // C, U, cbase: the culled / unculled counts, first sorted position
-    uint32_t node_base, full, extra, numbering;  // (accel_layout.hpp TreeLayout, LevelOrder / PreOrder)
-};
-static_assert(sizeof(AccelDevLayout) == 48, "the kernels' record");
+// released by drop() or with the owner.  (AccelDevLayout, a covered object as a refit takes it:
+// accel_layout.hpp.)
 
 // What eray_scene_refit_ray_accel_async works in (accel_dev.hip accel_refit_workspace): one device
 // allocation that lives from the first eligible call outside a capture until the next build or
@@ -165,6 +157,9 @@ struct RayAccel {
     // levels in one launch (a setting of eray_debug_set_refit_top_levels: it outlives drop())
     RefitWorkspace refit;
     bool refit_top_levels = true;
+    size_t device_bytes() const {  // of the four arrays as allocated
+        return sizeof(accel::Object) * objs.cap + sizeof(accel::Node) * nodes.cap + sizeof(accel::Hot) * hot.cap + 4 * index.cap;
+    }
     void drop() {
         refit.release();
         valid = false;

@@ -23,7 +23,15 @@
 //              the build's (they depend on face indices only)
 //   moved      nodes whose bytes differ between A's tree and the refitted one (the refit did work)
 //   caught     how many of the named corruptions of the refitted tree the checker names
-// and one line per class change that the refit must refuse (detected=1).
+// one line per class change that the refit must refuse (detected=1), and one line for a scene of three
+// objects, the middle one below min_faces, built by accel_build.cpp's build_scene as
+// eray_scene_build_ray_accel_refittable builds it:
+//   slices     1 when every covered object's slice of the concatenated arrays and its record are
+//              build_object's alone at those bases, and the uncovered object's record is zero
+//   layout     1 when every AccelDevLayout field is what the scene's sizes and tree_layout give
+//   refit      1 when the refit of the unmoved scene through that layout, emulated as the kernels run
+//              it over the scene's arrays, reproduces them byte for byte
+//   c0, extra0, c2, extra2: the covered objects' culled counts and nodes of level `full` that split
 #include "accel_emul.hpp"
 
 using namespace eray::accel;
@@ -122,8 +130,8 @@ bool emulate_refit_preorder(const std::vector<Hot>& faces, const Built& built, u
         else status = true;
     }
     if (!refit_keeps(nc, nu, status ? 1u : 0u, C, U)) return false;
+    if (!fits_tree_layout(built, T)) return false;  // (what build_scene checks before it records a layout)
     const TreeLayout t = tree_layout(C);
-    if (t.nodes != built.nodes.size() || t.depth != built.depth) return false;  // (what capi.cpp checks before it records a layout)
     std::vector<Node> nodes((size_t)node_base + t.nodes);
     std::vector<NodeBounds> bounds(nodes.size());
     for (uint32_t level = t.depth; level-- > 0;)  // levels, deepest first
@@ -220,6 +228,121 @@ bool refused(const char* name, const std::vector<float>& posA, Change change) {
     return detected;
 }
 
+// ---- a scene through build_scene ------------------------------------------------------------------
+// The first faces of a soup that hold exactly `culled` culled ones.
+std::vector<Hot> soup_with_culled(uint32_t culled) {
+    const std::vector<Hot> all = records(soup(2 * culled + 64, 0.8, 0.06));
+    std::vector<Hot> out;
+    for (uint32_t f = 0, c = 0; f < all.size() && c < culled; ++f) {
+        out.push_back(all[f]);
+        c += face_margin_of(all[f]).culled;
+    }
+    return out;
+}
+
+// The refit kernels' passes over a scene's arrays (accel_dev.hip accel_refit_device), every id and
+// range from the layout records: false on a class change.
+bool emulate_scene_refit(const std::vector<Hot>& faces, const std::vector<eray::gpu::AccelDevLayout>& layout, uint32_t max_depth,
+                         SceneBuilt* sc) {
+    std::vector<double> ab(2 * sc->hot.size());
+    std::vector<NodeBounds> bounds(sc->nodes.size());
+    std::vector<double> gamma(layout.size(), 0.0);
+    for (size_t o = 0; o < layout.size(); ++o) {  // margin and check passes
+        const eray::gpu::AccelDevLayout& ob = layout[o];
+        std::vector<char> unculled(ob.faces);
+        uint32_t nc = 0, nu = 0, status = 0;
+        for (uint32_t k = 0; k < ob.faces; ++k) {
+            const FaceMargin m = face_margin_of(faces[ob.hot_begin + k]);
+            unculled[k] = !m.culled;
+            ab[2 * (size_t)(ob.gbegin + k)] = m.alpha;
+            ab[2 * (size_t)(ob.gbegin + k) + 1] = m.beta;
+            (m.culled ? nc : nu) += 1;
+            if (m.culled) gamma[o] = std::fmax(gamma[o], m.gamma);
+        }
+        for (uint32_t k = 0; k < ob.U; ++k) {
+            const uint32_t slot = ob.gbegin + k, f = sc->index[slot];
+            if (f < ob.faces && unculled[f]) sc->hot[slot] = faces[ob.hot_begin + f];
+            else status = 1;
+        }
+        if (!refit_keeps(nc, nu, status, ob.C, ob.U)) return false;
+    }
+    for (uint32_t level = max_depth; level-- > 0;)  // levels, deepest first, every covered object
+        for (const eray::gpu::AccelDevLayout& ob : layout) {
+            const TreeLayout t{ob.C, ob.full, ob.extra, 0u, 0u};
+            for (uint32_t j = 0; j < (1u << level); ++j)
+                level_node<PreOrder>(t, level, j, sc->index.data() + ob.gbegin + ob.U, 0u, faces.data() + ob.hot_begin,
+                                     ab.data() + 2 * (size_t)ob.gbegin, ob.node_base, ob.gbegin + ob.U, sc->nodes.data(), bounds.data(),
+                                     sc->hot.data(), sc->index.data());
+        }
+    for (size_t o = 0; o < layout.size(); ++o)
+        sc->objs[layout[o].index] = refit_object(true, layout[o].C, layout[o].U, layout[o].node_base, layout[o].gbegin, gamma[o]);
+    return true;
+}
+
+bool scene_of_three() {
+    // C just above kLeafFaces << 6 (a pairs level), a few faces, C an exact kLeafFaces << 6
+    const std::vector<std::vector<Hot>> parts = {soup_with_culled((kLeafFaces << 6) + 3), records(soup(10, 0.8, 0.06)),
+                                                 soup_with_culled(kLeafFaces << 6)};
+    const uint32_t min_faces = 64;
+    std::vector<Hot> faces;
+    std::vector<uint32_t> sizes;
+    for (const std::vector<Hot>& p : parts) {
+        faces.insert(faces.end(), p.begin(), p.end());
+        sizes.push_back((uint32_t)p.size());
+    }
+    SceneBuilt sc;
+    size_t bad_object = 0;
+    const char* why = "";
+    if (!build_scene(faces.data(), sizes.data(), sizes.size(), min_faces, true, &sc, &bad_object, &why)) {
+        std::printf("  build_scene: object %zu: %s\n", bad_object, why);
+        return false;
+    }
+    // what the records must say, from the sizes, the faces' classes and tree_layout alone
+    bool slices = sc.objs.size() == sizes.size(), layout = true;
+    uint32_t begin = 0, gbegin = 0, blocks = 0, cbase = 0, node_base = 0, covered = 0, depth = 0, c[3] = {}, extra[3] = {};
+    for (size_t i = 0; slices && i < sizes.size(); begin += sizes[i], ++i) {
+        const uint32_t n = sizes[i];
+        static const Object none{};
+        if (n < min_faces) {
+            slices = !std::memcmp(&sc.objs[i], &none, sizeof(Object));
+            continue;
+        }
+        uint32_t C = 0;
+        for (uint32_t k = 0; k < n; ++k) C += face_margin_of(faces[begin + k]).culled;
+        const TreeLayout t = tree_layout(C);
+        c[i] = C;
+        extra[i] = t.extra;
+        Built alone;
+        slices = host_build(parts[i], node_base, gbegin, &alone) && alone.nodes.size() == t.nodes && alone.hot.size() == n &&
+                 sc.nodes.size() >= (size_t)node_base + t.nodes && sc.hot.size() >= (size_t)gbegin + n && sc.index.size() == sc.hot.size() &&
+                 !std::memcmp(&sc.nodes[node_base], alone.nodes.data(), sizeof(Node) * t.nodes) &&
+                 !std::memcmp(&sc.hot[gbegin], alone.hot.data(), sizeof(Hot) * n) &&
+                 !std::memcmp(&sc.index[gbegin], alone.index.data(), 4 * (size_t)n) && !std::memcmp(&sc.objs[i], &alone.obj, sizeof(Object));
+        const eray::gpu::AccelDevLayout want{begin, n, gbegin, blocks, (uint32_t)i, C, n - C, cbase, node_base, t.full, t.extra, 1u};
+        layout = layout && covered < sc.layout.size() && !std::memcmp(&sc.layout[covered], &want, sizeof want);
+        ++covered;
+        gbegin += n;
+        blocks += (n + 255u) / 256u;
+        cbase += C;
+        node_base += t.nodes;
+        depth = std::max(depth, t.depth);
+    }
+    slices = slices && sc.nodes.size() == node_base && sc.hot.size() == gbegin;
+    layout = layout && sc.layout.size() == covered && sc.objects == covered && sc.max_depth == depth && sc.faces == gbegin &&
+             sc.unculled == gbegin - cbase;
+    // the refit of the unmoved scene: the nodes start from zero, so every one must be written
+    SceneBuilt again = sc;
+    std::fill(again.nodes.begin(), again.nodes.end(), Node{});
+    std::memset(again.objs.data(), 0, sizeof(Object) * again.objs.size());
+    const bool refit = slices && layout && emulate_scene_refit(faces, sc.layout, sc.max_depth, &again) &&
+                       !std::memcmp(again.nodes.data(), sc.nodes.data(), sizeof(Node) * sc.nodes.size()) &&
+                       !std::memcmp(again.hot.data(), sc.hot.data(), sizeof(Hot) * sc.hot.size()) && again.index == sc.index &&
+                       !std::memcmp(again.objs.data(), sc.objs.data(), sizeof(Object) * sc.objs.size());
+    std::printf("scene=three_objects objects=%u faces=%u nodes=%zu depth=%u c0=%u extra0=%u c2=%u extra2=%u slices=%d layout=%d refit=%d\n",
+                sc.objects, gbegin, sc.nodes.size(), sc.max_depth, c[0], extra[0], c[2], extra[2], (int)slices, (int)layout, (int)refit);
+    return slices && layout && refit;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -274,6 +397,7 @@ int main(int argc, char** argv) {
         }
         return -1;
     });
+    ok &= scene_of_three();  // (last: its meshes draw from the generator after every figure above)
     std::printf(ok ? "OK\n" : "FAILED\n");
     return ok ? 0 : 1;
 }

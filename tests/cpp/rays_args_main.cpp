@@ -1,5 +1,5 @@
 // Stand-alone checker of eray_cast_rays' argument validation (eray_amd/csrc/rays_args.hpp, the
-// function capi.cpp calls), meant for the host sanitizers and a machine without a GPU:
+// function capi_rays.cpp calls), meant for the host sanitizers and a machine without a GPU:
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 //       -Iinclude tests/cpp/rays_args_main.cpp -Leray_amd/lib -leray_hip \

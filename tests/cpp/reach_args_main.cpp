@@ -1,5 +1,5 @@
 // Stand-alone checker of eray_rays_reach_light's argument validation (check_reach_params in
-// eray_amd/csrc/rays_args.hpp, the function capi.cpp calls), meant for the host sanitizers and a
+// eray_amd/csrc/rays_args.hpp, the function capi_rays.cpp calls), meant for the host sanitizers and a
 // machine without a GPU:
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \

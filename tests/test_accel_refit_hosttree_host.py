@@ -6,8 +6,11 @@ builds meshes with accel_build.cpp's build_object at non-zero bases and refits t
 level_node<PreOrder>, step for step as the refit kernels run: with unmoved faces the refit is the
 build byte for byte; after a deformation accel::check accepts the tree, the walk equals the linear scan
 and the words that depend on face indices alone are the build's; single faces that change class make
-the refit refuse; the checker names the nine corruptions on a refitted host tree.  The program is also
-compiled with -fsanitize=address,undefined and run as a program of its own."""
+the refit refuse; the checker names the nine corruptions on a refitted host tree.  A scene of three
+objects goes through accel_build.cpp's build_scene, the code eray_scene_build_ray_accel_refittable runs
+between its download and its uploads: the arrays are build_object's per covered object, the layout
+records what the sizes and tree_layout give, and a refit through them reproduces the arrays.  The
+program is also compiled with -fsanitize=address,undefined and run as a program of its own."""
 import ctypes as C
 import os
 import re
@@ -89,6 +92,14 @@ def test_checker_names_every_corruption_of_a_refitted_host_tree(emulation):
     m = re.search(r"^corruptions_named=(\S*)$", r.stdout, re.M)
     assert m and set(m.group(1).split(",")) == CORRUPTIONS, r.stdout
     assert fig["slivers3000"]["caught"] == len(CORRUPTIONS)
+
+
+def test_scene_build_concatenates_the_objects_and_records_the_layout_a_refit_reproduces_it_from(emulation):
+    r, _ = emulation
+    f = figures(r.stdout, key="scene")["three_objects"]
+    assert f["slices"] == 1 and f["layout"] == 1 and f["refit"] == 1, f
+    # two covered objects around one below min_faces; a tree with a pairs level and one without
+    assert f["objects"] == 2 and f["c0"] == 259 and f["extra0"] == 3 and f["c2"] == 256 and f["extra2"] == 0, f
 
 
 def test_emulation_under_asan_ubsan(sphere_file, tmp_path):
