@@ -24,8 +24,8 @@ OBJ = os.path.join(PKG, "_obj")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "liberay_hip.so")
 
-SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "capi_rays.cpp", "comm.cpp",
-           "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
+SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "capi_setup.cpp",
+           "capi_frames.cpp", "capi_rays.cpp", "comm.cpp", "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
             f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),

@@ -525,7 +525,7 @@ __device__ __forceinline__ void max4(uint32_t* dst, const uint32_t (&a)[4]) {
 // face index: bins of up to kSortWave entries one wave each, longer ones (the poles of the 1M-face
 // stand-in put 300-700 entries into a few bins) one workgroup each.  The frame kernel relies on
 // it: in a bin of 65 to kBinSortMax entries the position order is the face order
-// (render.hip first_hit_binned / first_hit_binned_wave), and chunk c's first two entries carry the
+// (frame_first_hit.hpp first_hit_binned / first_hit_binned_wave), and chunk c's first two entries carry the
 // union of the masks of chunks c + 1 .. (BinEntry::pad): pixels outside it cannot be hit by
 // anything later in the bin.
 constexpr uint32_t kSortMax = kBinSortMax;

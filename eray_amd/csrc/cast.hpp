@@ -85,6 +85,8 @@ __device__ __forceinline__ void closer(Hit& h, uint32_t oi, int f, float u, floa
 
 // The hit's Level: Triangle::intersects' P and N (primitives.rs:60-69), RaycastHit's UV and
 // Material::get (object.rs:70-74, material.rs:56-94).
+// (frame_sub.hpp's render_sub holds this, shade and walk's ambient term once more, for camera rays.  Apart on purpose:
+// as functions shared with it they changed frame_kernel's code, registers and spills included)
 __device__ void fill_level(const FrameParams& p, f3 o, f3 d, const Hit& h, Level& L) {
     const float bu = h.u, bv = h.v, bt = h.t;
     const ObjectDesc& od = p.objects[h.o];

@@ -635,7 +635,7 @@ int eray_gather_rows(eray_ctx* ctx, void* nccl_comm, const uint8_t* local, uint8
     ncclResult_t r = ncclCommCount(c, &nranks);
     if (r == ncclSuccess) r = ncclCommUserRank(c, &rank);
     if (r != ncclSuccess) return nccl_error(ctx, "gather: communicator", r);
-    if (band_rows && (band_rows < 4 || (band_rows & (band_rows - 1))))  // as eray_render's bands (capi.cpp)
+    if (band_rows && (band_rows < 4 || (band_rows & (band_rows - 1))))  // as eray_render's bands (capi_frames.cpp)
         return eray_internal_error(ctx, ERAY_E_INVALID_ARGUMENT, "gather: band_rows must be a power of two >= 4");
     if (!band_rows && height % (uint32_t)nranks)
         return eray_internal_error(ctx, ERAY_E_INVALID_ARGUMENT, "gather: height does not split into equal blocks");

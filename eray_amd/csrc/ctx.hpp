@@ -1,7 +1,10 @@
 // ctx.hpp — the context behind include/eray_hip.h's eray_ctx handle and what the C-ABI translation
-// units (capi.cpp: context, scene, frames; capi_rays.cpp: ray queries and their hierarchy) share to
-// work on it: the error policy (set_error, HIP_TRY, use_device) and the scene upload.  Private to
-// those two files; comm.cpp and objload.cpp reach the context through internal.hpp's eray_internal_*.
+// units share to work on it: capi.cpp (context, memory, shaderlib nodes, scene, the eray_internal_*
+// and eray_debug_* hooks), capi_setup.cpp (camera setup, bins, frame tags), capi_frames.cpp (the
+// frame entry points) and capi_rays.cpp (ray queries and their hierarchy).  Here: the error policy
+// (set_error, HIP_TRY, use_device), the scene upload, and what the other units need of
+// capi_setup.cpp — declared here and nowhere else.  Private to those four files; comm.cpp and
+// objload.cpp reach the context through internal.hpp's eray_internal_*.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -210,6 +213,31 @@ inline int use_device(eray_ctx* ctx) {
 
 // Uploads what changed of the scene (geometry, descriptors) on the context's stream (capi.cpp).
 int sync_scene(eray_ctx* ctx);
+
+// ---- the frame path's per-camera state (capi_setup.cpp) ----
+// The rendered rows of a call: camera rows [row0, row0 + rows), or rows local rows of
+// interleaved bands (eray_render_params::band_rows).
+struct RowSpan {
+    uint32_t row0, rows, band_shift, band_mask, band_stride;
+};
+RowSpan row_span(const eray_render_params* rp);
+// Source tags of rendered frames, and which PPM slots hold which (eray_gather_frames).
+FrameSource frame_source(uint32_t kind, uint64_t key, uint32_t W, uint32_t H, const RowSpan& rs);
+FrameSource scene_source(const eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs);
+void untag_range(eray_ctx* ctx, uintptr_t a, size_t bytes);
+void tag_frames(eray_ctx* ctx, const uint8_t* ppm, uint64_t stride, uint32_t n, const FrameSource& s);
+// Camera setups: one camera's, a path chunk's cameras at once, the scene camera's with its host copy.
+SetupParams setup_params(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint32_t H, const RowSpan& rs);
+int enqueue_setup(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint32_t H, const RowSpan& rs, bool ordered,
+                  bool keep_all = false, int32_t* path_union = nullptr);
+int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs);
+int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_cams, uint32_t ncam, uint32_t W,
+                        uint32_t H, const RowSpan& rs, hipStream_t s, int32_t* path_union = nullptr);
+bool batch_setup_ok(const eray_ctx* ctx);
+CamDev cam_dev(const eray_camera& c);
+void state_arrived(eray_ctx* ctx);
+int sync_setup(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs, bool wait, bool* known,
+               bool trace_bins = false);
 
 // (owners.hpp)
 template <typename T>

@@ -1,4 +1,4 @@
-// internal.hpp — descriptors shared by the C-ABI layer (capi.cpp, capi_rays.cpp) and the gfx950 kernels.
+// internal.hpp — descriptors shared by the C-ABI layer (capi*.cpp) and the gfx950 kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -84,7 +84,7 @@ constexpr uint32_t kBinW = 16, kBinH = 4;
 // ones keep the scatter's order.  In a sorted bin each full 64-entry chunk but the last also
 // carries, in the pad words of its first two entries (low, high half), the union of the pixel
 // masks of every later chunk: the frame kernel stops the bin once no pixel that can still improve
-// is covered by what is left (render.hip first_hit_binned_wave).
+// is covered by what is left (frame_first_hit.hpp first_hit_binned_wave).
 constexpr uint32_t kBinSortMax = 1024;
 // Detail rectangles carried in the kernel arguments (more objects: merged into the last one).
 constexpr int kMaxRects = 8;
@@ -93,7 +93,7 @@ constexpr uint32_t kMaxBounces = 16;
 // Frames one launch may render (eray_frame_ring::frames_per_launch <= slots <= 64).
 constexpr uint32_t kMaxFramesPerLaunch = 64;
 // The frame kernel reads triangle records (TriHot 48 B, TriShade 64 B) and bin entries (64 B) by
-// buffer loads with 32-bit byte offsets (render.hip load_rec): a scene holds fewer than 2^26
+// buffer loads with 32-bit byte offsets (frame_scene.hpp load_rec): a scene holds fewer than 2^26
 // triangles (eray_scene_add_object refuses more) and a bin buffer at most 2^26 entries (a setup
 // that needs more overflows: its objects are scanned through LDS tiles, still exact).
 constexpr uint64_t kMaxSceneTris = (1ull << 26) - 1;

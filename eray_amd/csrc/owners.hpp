@@ -56,7 +56,7 @@ struct Stream : Handle<hipStream_t, hipStreamDestroy> {
 using Graph = Handle<hipGraph_t, hipGraphDestroy>;
 using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
 
-// A captured launch plan with the key it was captured for (capi.cpp ensure_graph).
+// A captured launch plan with the key it was captured for (capi_frames.cpp ensure_graph).
 struct FrameGraph {
     Graph graph;
     GraphExec exec;  // (destroyed before its graph)

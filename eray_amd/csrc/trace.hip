@@ -288,7 +288,7 @@ constexpr uint32_t kSkipTris = kTraceSkipTris;
 
 // The records, once per camera and scene (one workgroup; the host passes trace_cull only for
 // scenes of at most kSkipTris faces, and launches it when the camera or the scene changed:
-// capi.cpp prepare_render — not in every frame's graph, C2 with AA = 4: 56 -> 47 us per frame).
+// capi_frames.cpp prepare_render — not in every frame's graph, C2 with AA = 4: 56 -> 47 us per frame).
 __global__ void __launch_bounds__(256) trace_cull_kernel(FrameParams p) {
     const uint32_t i = threadIdx.x;
     if (i >= p.total_tris) return;

@@ -2,12 +2,15 @@
 # Diagnostics: a same-source variant of the product library for a same-box A/B.
 #   scripts/build_variant.sh NAME SOURCE 'SED-EXPRESSION' ['SED-EXPRESSION' ...]
 #   scripts/build_variant.sh NAME SOURCE --from FILE   (FILE replaces eray_amd/csrc/SOURCE)
+# SOURCE: any name of eray_amd/build.py's SOURCES, whose objects are the ones linked.
 # compiles eray_amd/csrc/SOURCE with the sed edits applied (into eray_amd/_obj/variant_NAME.o) and
 # links it with the product's other objects -> eray_amd/lib/liberay_hip_NAME.so.  Fails when an
 # edit matches nothing (the variant would silently equal the product).
 set -eu
 cd "$(dirname "$0")/.."
 NAME=$1; SRC=$2; shift 2
+SOURCES=$(python -c 'from eray_amd.build import SOURCES; print(" ".join(SOURCES))')  # the product's own list
+case " $SOURCES " in *" $SRC "*) ;; *) echo "SOURCE must be one of: $SOURCES" >&2; exit 1;; esac
 python -m eray_amd.build > /dev/null
 O=eray_amd/_obj
 TMP=eray_amd/csrc/_variant_$NAME.${SRC##*.}
@@ -22,7 +25,7 @@ F="-O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function --offload-a
 case $SRC in *.cpp) LANG="-x hip";; *) LANG="";; esac
 hipcc $F $LANG -c $TMP -o $O/variant_$NAME.o
 objs=""
-for s in render.hip setup.hip trace.hip bins.hip shaderlib.hip capi.cpp comm.cpp objload.cpp; do
+for s in $SOURCES; do
   [ $s = $SRC ] && objs="$objs $O/variant_$NAME.o" || objs="$objs $O/$s.o"
 done
 hipcc --offload-arch=gfx950 -shared -fPIC -o eray_amd/lib/liberay_hip_$NAME.so $objs -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib

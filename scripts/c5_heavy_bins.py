@@ -1,7 +1,7 @@
 """Where a C5 share's heavy bins end (diagnostics): for one rank of the 8-GPU
 band split, rendered alone on one GPU, every own bin of more than one 64-entry chunk is dumped
 (eray_debug_bin_dump: faces in bin order, pixel masks) and replayed on the host against the
-frame's first-hit faces: the chunk after which render.hip first_hit_binned_wave's sorted-bin exit
+frame's first-hit faces: the chunk after which frame_first_hit.hpp first_hit_binned_wave's sorted-bin exit
 fires (no pixel whose best position is still ahead is covered by a later chunk's mask), and what
 holds it there — a pixel whose winning face sits late in the bin, or a pixel no face hits that a
 later face's mask still covers.

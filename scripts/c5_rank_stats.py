@@ -66,7 +66,7 @@ def main() -> None:
         rect = (C.c_int32 * 4)()
         assert lib.eray_debug_setup_state(ctx._h, 0, C.byref(cs), rect) == 0
         # this rank's own bin rows (camera rows 4 r + 32 k .. + 3; at phase 0 camera row y is in bin
-        # row y / 4 + 1, internal.hpp / render.hip's bin index)
+        # row y / 4 + 1, internal.hpp / frame_sub.hpp's bin index)
         nb = C.c_uint32()
         cnt = np.zeros(st[0], np.uint32)
         assert lib.eray_debug_bin_counts(ctx._h, 0, cnt.ctypes.data_as(C.POINTER(C.c_uint32)), int(st[0]), C.byref(nb)) == 0

@@ -11,7 +11,7 @@ import numpy as np
 WAVE_CAPACITY = 8192 * 256          # shaderlib.hip:23 (grid_for1): at most 8192 workgroups of kBlock = 256
 MATERIAL_CAPACITY = 2 * 8192 * 256  # the same grid, shaderlib.hip:203: kMatTexels = 2 texels per thread
 VEC_CAPACITY = 2048 * 256 * 4       # shaderlib.hip:29 (grid_for): at most 2048 workgroups of kBlock x kVec = 4
-PACK_CAPACITY = 2048 * 256          # render.hip:2102 (launch_pack_ppm): at most 2048 workgroups of 256
+PACK_CAPACITY = 2048 * 256          # render.hip launch_pack_ppm: at most 2048 workgroups of 256
 WAVE_SHAPE = (1531, 1801)           # w, h
 MATERIAL_SHAPE = (2311, 2203)
 VEC_SHAPE = (2051, 1031)            # rgb, flat, mix

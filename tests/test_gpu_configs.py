@@ -308,7 +308,7 @@ def _bin_entries(gpu, b, cap=1024):
 
 
 def test_c5_sorted_bins_carry_later_chunk_masks(gpu, synth1m):
-    """C5's bins (1M faces, 7680x4320) as render.hip first_hit_binned_wave relies on them
+    """C5's bins (1M faces, 7680x4320) as frame_first_hit.hpp first_hit_binned_wave relies on them
     (bins.hip bin_sort_kernel): every bin of 65..1024 entries lists its faces in increasing index —
     including those of more than 256 entries, sorted by a whole workgroup — and the first two
     entries of each chunk but the last hold the low and high half of the union of the masks of the

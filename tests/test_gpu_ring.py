@@ -85,7 +85,7 @@ def test_static_ring_every_slot_is_the_frame(gpu, cube, per_launch):
 
 def test_ring_beyond_the_infinity_cache(gpu, cube):
     """A ring whose slots together exceed the 256 MiB Infinity Cache (16 slots of 1920x1080: 630 MB)
-    takes the unpaced per-lane-coordinate fill (render.hip kLaunchRingBeyondCache): every slot is
+    takes the unpaced per-lane-coordinate fill (frame_fill.hpp fill_frames, kLaunchRingBeyondCache): every slot is
     still the frame eray_render writes."""
     W, H = 1920, 1080
     sc = MainScene(gpu, *cube, W, H, texture=256, fov=(16.0, 9.0))

@@ -1,4 +1,4 @@
-"""The frame kernel's single-object path (render.hip render_sub<kOne>: a small scene of one object
+"""The frame kernel's single-object path (frame_sub.hpp render_sub<kOne>: a small scene of one object
 runs a build without the object loops, the closest-object compare and the per-lane object
 selection, its ObjGeom read once per sub-block and reused by the shadow test) against the CPU oracle.
 
