@@ -37,6 +37,7 @@ RENDER_NO_DENSE_DETAIL = 4
 RENDER_SEPARATE_FILL = 8
 RENDER_NO_SEPARATE_FILL = 16
 RENDER_SHARED_DETAIL = 32
+RENDER_NO_RAY_ACCEL = 64  # the general tracer ignores the ray-query hierarchy (A/B; the same frame)
 
 GATHER_DEFAULT = 0
 GATHER_SCENE_CAMERA = 1
@@ -281,13 +282,14 @@ DEBUG_SIGNATURES = {
     "eray_debug_ray_accel_check": (C.c_int, [_P, C.c_char_p, _U]),
     "eray_debug_ray_accel_arrays": (C.c_int, [_P, _U, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "eray_debug_set_refit_top_levels": (C.c_int, [_P, C.c_int]),
+    "eray_debug_trace_ray_accel": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
 }
 
 # Entry points a library selected by ERAY_LIB may predate (scripts/rays_bench.py --secondary runs the
 # parent commit's build): absent there, they stay unbound; the product library must have them all.
 _AB_OPTIONAL = {"eray_rays_reach_light", "eray_scene_update_object", "eray_scene_refit_ray_accel",
                 "eray_scene_object_triangle_count", "eray_scene_refit_ray_accel_async", "eray_scene_ray_accel_refit_status",
-                "eray_scene_build_ray_accel_refittable"}
+                "eray_scene_build_ray_accel_refittable", "eray_debug_trace_ray_accel"}
 
 _lib = None
 
@@ -704,6 +706,13 @@ class Context:
         """eray_debug_set_refit_top_levels (diagnostics): the async refit's upper levels in one launch
         (the default) or a launch per level; the same bytes."""
         self._check(lib().eray_debug_set_refit_top_levels(self._h, 1 if on else 0))
+
+    def trace_ray_accel_objects(self) -> int:
+        """eray_debug_trace_ray_accel: the objects the last general-tracer render (anti-aliasing or
+        bounces) searched through the ray-query hierarchy; 0: its shadow and reflected rays scanned."""
+        n = C.c_uint32()
+        self._check(lib().eray_debug_trace_ray_accel(self._h, C.byref(n)))
+        return n.value
 
     def render(self, image_width, image_height, row0=0, rows=None, out_rgb=None, out_ppm=None,
                out_face=None, bounces=0, anti_aliasing=0, flags=RENDER_DEFAULT, aa_seed=0, band_rows=0,

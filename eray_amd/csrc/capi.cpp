@@ -446,6 +446,7 @@ int eray_scene_reset(eray_ctx* ctx) {
     ctx->geom_dirty = ctx->desc_dirty = true;
     ctx->ray_accel.valid = false;
     ctx->ray_accel.scene_changed = true;
+    ++ctx->ray_accel.gen;
     return ERAY_OK;
 }
 
@@ -556,6 +557,7 @@ int eray_scene_add_object(eray_ctx* ctx, const eray_object* obj, uint32_t* index
     ctx->geom_dirty = ctx->desc_dirty = true;
     ctx->ray_accel.valid = false;
     ctx->ray_accel.scene_changed = true;
+    ++ctx->ray_accel.gen;
     return ERAY_OK;
 }
 

@@ -14,6 +14,21 @@
 
 namespace {
 enum class SetupWait { kNo, kYes };
+
+// Does a general-tracer render search through the scene's ray-query hierarchy (trace.hip's kernels
+// with a RayAccelView)?  When the hierarchy is valid, covers an object, no flag forbids it, and some
+// covered object's bounding box is not a point in x and y.  The last condition: almost every shadow
+// and reflected ray fails BoundingBox::intersects on such a box (hit.hpp point_box_rejects; the
+// reference's loaded meshes carry a (0,0,0) box), so with nothing but such boxes no walk would ever
+// start and the hierarchy kernels' registers and LDS would buy nothing.  The number of covered
+// objects, 0 for the scan.
+uint32_t trace_accel_objects(const eray_ctx* ctx, uint32_t flags) {
+    const RayAccel& ra = ctx->ray_accel;
+    if (!ra.valid || !ra.covered || (flags & (ERAY_RENDER_BRUTE_FORCE | ERAY_RENDER_NO_RAY_ACCEL))) return 0u;
+    for (const HostObject& o : ctx->objects)
+        if (o.T >= ra.min_faces && !(o.lo[0] == o.hi[0] && o.lo[1] == o.hi[1])) return ra.covered;
+    return 0u;
+}
 // Frame parameters of a render call.  Culled frames need the camera's setup: when its results
 // are on the host (or `wait`), the detail rectangles / count travel in the kernel arguments
 // (args mode); otherwise the frame kernel reads them from the setup's CamState (device-camera
@@ -21,6 +36,7 @@ enum class SetupWait { kNo, kYes };
 int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out, bool* empty,
                    SetupWait wait = SetupWait::kNo) {
     if (int st = use_device(ctx)) return st;
+    ctx->lc.accel = RayAccelView{nullptr, nullptr, nullptr, nullptr};  // (chosen below, per call)
     if (!rp) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "params is null");
     // anti-aliasing and reflection bounces take the general tracer (trace.hip); bounces only
     // matter when some material has a reflection output (engine.rs:181-182)
@@ -29,7 +45,8 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
         return set_error(ctx, ERAY_E_UNSUPPORTED, "bounces = %u: at most %u reflection levels", rp->bounces,
                          kMaxBounces);
     const uint32_t known_flags = ERAY_RENDER_BRUTE_FORCE | ERAY_RENDER_DENSE_DETAIL | ERAY_RENDER_NO_DENSE_DETAIL |
-                                 ERAY_RENDER_SEPARATE_FILL | ERAY_RENDER_NO_SEPARATE_FILL | ERAY_RENDER_SHARED_DETAIL;
+                                 ERAY_RENDER_SEPARATE_FILL | ERAY_RENDER_NO_SEPARATE_FILL | ERAY_RENDER_SHARED_DETAIL |
+                                 ERAY_RENDER_NO_RAY_ACCEL;
     if (rp->flags & ~known_flags) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "unknown render flags 0x%x", rp->flags);
     const bool general = rp->anti_aliasing > 0 || bounces > 0;
     uint32_t W, H;
@@ -130,6 +147,10 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
         }
     }
     p.trace_bins = trace_bins ? 1u : 0u;
+    if (general) {  // the tracer's shadow and reflected rays through the hierarchy, or the scan
+        ctx->trace_accel_objects = trace_accel_objects(ctx, rp->flags);
+        if (ctx->trace_accel_objects) ctx->lc.accel = accel_view(ctx);
+    }
     // the setup's detail sub-block list (ordered: heavy ones first), the frame kernel's for binned
     // objects or the tracer's (trace.hip trace_binned_kernel, trace_heavy_kernel)
     if (trace_bins || (cull && ctx->binned)) {
@@ -137,7 +158,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
         p.detail_heavy = ctx->bins.dcount;
         p.detail_occ = ctx->bins.docc;
     }
-    p.launch_flags = rp->flags & ~(ERAY_RENDER_BRUTE_FORCE | kLaunchRingBeyondCache);
+    p.launch_flags = rp->flags & ~(ERAY_RENDER_BRUTE_FORCE | ERAY_RENDER_NO_RAY_ACCEL | kLaunchRingBeyondCache);
     if (!cull) {  // every pixel in detail: one rectangle, the frame (sub-block units)
         if (p.nobj) {
             p.nrect = 1;
@@ -174,6 +195,13 @@ FrameSource render_source(const eray_ctx* ctx, const FrameParams& p, const eray_
 }  // namespace
 
 extern "C" {
+
+// (diagnostics, eray_hip_debug.h) what prepare_render chose for the last general-tracer render
+int eray_debug_trace_ray_accel(eray_ctx* ctx, uint32_t* objects) {
+    if (!ctx || !objects) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "eray_debug_trace_ray_accel: null argument");
+    *objects = ctx->trace_accel_objects;
+    return ERAY_OK;
+}
 
 int eray_render(eray_ctx* ctx, const eray_render_params* rp) {
     FrameParams p;
@@ -449,6 +477,18 @@ std::vector<unsigned char> ring_key(std::vector<unsigned char> key, const Ring& 
     return key;
 }
 
+// The hierarchy the call's tracer launches hold (LaunchCtx::accel, not part of FrameParams): its
+// four addresses and the hierarchy's generation, which every build, drop, add_object and reset
+// advances — so a plan captured with arrays that have since been released is never found again,
+// even where an allocation returns an old address.  A refit in place keeps both, and the plan.
+// Without a hierarchy in the launches: zeros.
+std::vector<unsigned char> accel_key(std::vector<unsigned char> key, const eray_ctx* ctx) {
+    const RayAccelView& a = ctx->lc.accel;
+    for (const void* ptr : {(const void*)a.objs, (const void*)a.nodes, (const void*)a.hot, (const void*)a.index}) append(key, ptr);
+    append(key, a.objs ? ctx->ray_accel.gen : (uint64_t)0);
+    return key;
+}
+
 // The frames of a call with the scene camera into a ring: frame f is rendered by the launch of
 // frame f - f % per_launch.
 struct StaticRing {
@@ -458,7 +498,7 @@ struct StaticRing {
     uint32_t frames;
     int plan(Plan* out) const {
         auto frame = [this](uint32_t f, uint32_t n) { return body(0, f, n); };
-        return ensure_plan(ctx, ring_key(params_key(p, 0), r), frames, frame, out);
+        return ensure_plan(ctx, accel_key(ring_key(params_key(p, 0), r), ctx), frames, frame, out);
     }
     int before_chunk(uint32_t, uint32_t) const { return ERAY_OK; }
     int body(uint32_t, uint32_t f, uint32_t n) const {

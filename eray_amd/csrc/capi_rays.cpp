@@ -32,14 +32,6 @@ int begin_build(eray_ctx* ctx, Clock::time_point* t0) {
     return ERAY_OK;
 }
 
-// The hierarchy as the query kernels take it: none unless it is valid (never a stale tree: every
-// geometry change clears `valid`).
-RayAccelView accel_view(const eray_ctx* ctx) {
-    const RayAccel& ra = ctx->ray_accel;
-    if (!ra.valid) return RayAccelView{nullptr, nullptr, nullptr, nullptr};
-    return RayAccelView{ra.objs, ra.nodes, reinterpret_cast<const TriHot*>((const eray::accel::Hot*)ra.hot), ra.index};
-}
-
 }  // namespace
 
 extern "C" {
@@ -150,6 +142,7 @@ int build_accel_host(eray_ctx* ctx, uint32_t min_faces, Clock::time_point t0, er
         ra.min_faces = min_faces;
         ra.node_count = b.nodes.size();
         ra.slot_count = b.hot.size();
+        ra.covered = out.objects;
         ra.builder = refittable ? RayAccel::kHostRefittable : RayAccel::kHost;
         if (refittable) {
             ra.layout = std::move(b.layout);
@@ -197,6 +190,7 @@ int build_accel_device(eray_ctx* ctx, uint32_t min_faces, Clock::time_point t0, 
         ra.min_faces = min_faces;
         ra.node_count = dev.nodes;
         ra.slot_count = out.faces;
+        ra.covered = out.objects;
         ra.builder = RayAccel::kDevice;
         ra.valid = true;
     }

@@ -8,9 +8,10 @@
 // How an object's first face is found is the caller's: surface, reaches_light and walk take a
 // face finder, a callable (oi, ob, o, d, u, v, t) -> int that returns Object::intersects' face of
 // object oi (geometry ob) for Ray(o, d), -1 for none, with that face's u, v, t.  ScanFaces is the
-// per-lane scan (first_face) that trace.hip and rays.hip's rays_kernel use through the overloads
-// without a finder; rays_accel_kernel and reach_kernel pass one that goes through the ray-query
-// hierarchy.  Every finder returns the same face and the same bits.
+// per-lane scan (first_face) that trace.hip's kernels without a hierarchy and rays.hip's rays_kernel
+// use through the overloads without a finder; rays_accel_kernel, reach_kernel and trace.hip's
+// kernels with a hierarchy pass one that goes through the ray-query hierarchy (accel_faces.hpp).
+// Every finder returns the same face and the same bits.
 #pragma once
 
 #include "device_math.hpp"

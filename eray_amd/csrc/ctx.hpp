@@ -166,6 +166,9 @@ struct eray_ctx {
     Stream fill_stream;
     Event fill_fork, fill_join;
     LaunchCtx lc{nullptr, nullptr, nullptr};
+    // objects the last general-tracer render searched through the hierarchy (prepare_render sets it
+    // when it chooses lc.accel; 0: the per-lane scan) — eray_debug_trace_ray_accel
+    uint32_t trace_accel_objects = 0;
     Event update_join;  // eray_scene_update_object: the other streams' work so far, waited for by `stream`
 
     // Waits for the context's streams, then releases what the members do not own themselves.
@@ -191,6 +194,14 @@ inline bool scene_reflective(const eray_ctx* ctx) {
         reflective |= r >= 0 ? !texel_is_color(o.tnodes[r].kind) : o.mat.reflection.data != nullptr;
     }
     return reflective;
+}
+
+// The ray-query hierarchy as the kernels take it: none unless it is valid (never a stale tree: every
+// geometry change clears `valid`).
+inline RayAccelView accel_view(const eray_ctx* ctx) {
+    const RayAccel& ra = ctx->ray_accel;
+    if (!ra.valid) return RayAccelView{nullptr, nullptr, nullptr, nullptr};
+    return RayAccelView{ra.objs, ra.nodes, reinterpret_cast<const TriHot*>((const eray::accel::Hot*)ra.hot), ra.index};
 }
 
 // Records the message on the context (without one: for this thread, eray_last_error) and returns

@@ -411,6 +411,15 @@ constexpr uint32_t kLaunchDense = 2u, kLaunchNoDense = 4u, kLaunchSeparateFill =
                    kLaunchSharedDetail = 32u;
 // (internal, set per launch by the ring plan: the ring's slots together exceed the Infinity Cache)
 constexpr uint32_t kLaunchRingBeyondCache = 1u << 16;
+// The ray-query hierarchy of the scene (accel_walk.hpp; built by eray_scene_build_ray_accel): per
+// object a record (has == 0: the object keeps the LDS tiles), the nodes, and the leaf-ordered byte
+// copies of the face records with their original indices.  objs null: no hierarchy.
+struct RayAccelView {
+    const accel::Object* objs;
+    const accel::Node* nodes;
+    const TriHot* hot;
+    const uint32_t* index;
+};
 // Per-context launch resources: the separate fill kernel's stream and its fork / join events.
 // Measurement (eray_time_frames_ring): when frame_t[0] is set, the frame kernel is launched with
 // hipExtLaunchKernel's start / stop events, which take the dispatch's own begin / end timestamps
@@ -421,8 +430,13 @@ struct LaunchCtx {
     hipEvent_t frame_t[2] = {nullptr, nullptr};
     hipEvent_t fill_t[2] = {nullptr, nullptr};
     uint32_t* fill_used = nullptr;  // set to 1 when the launch ran the separate fill kernel
+    // the general tracer's face finder for shadow and reflected rays (trace.hip): the scene's valid
+    // hierarchy when the call's render takes it (capi_frames.cpp prepare_render sets it per call),
+    // objs null: the per-lane scan.  Not in FrameParams: the frame kernel's argument layout stays.
+    RayAccelView accel{nullptr, nullptr, nullptr, nullptr};
 };
-// The frame kernel, or the general tracer (trace.hip) when p.aa or p.bounces is set.
+// The frame kernel, or the general tracer (trace.hip) when p.aa or p.bounces is set (with
+// lc.accel's hierarchy, when it has one).
 hipError_t launch_render(const FrameParams& p, const LaunchCtx& lc, hipStream_t s);
 hipError_t launch_trace(const FrameParams& p, const LaunchCtx& lc, hipStream_t s);
 // Measurement (eray_time_write_ceiling): the frames' background bytes as one plain block-strided
@@ -447,15 +461,7 @@ struct RayBatch {
     uint4* out_hit;      // count x 3 words of 16 B (eray_ray_hit), or null
     float* out_rgb;      // count x 3, or null
 };
-// The ray-query hierarchy of the scene (accel_walk.hpp; built by eray_scene_build_ray_accel): per
-// object a record (has == 0: the object keeps the LDS tiles), the nodes, and the leaf-ordered byte
-// copies of the face records with their original indices.  objs null: no hierarchy.
-struct RayAccelView {
-    const accel::Object* objs;
-    const accel::Node* nodes;
-    const TriHot* hot;
-    const uint32_t* index;
-};
+// (RayAccelView, the hierarchy as the kernels take it: above, before LaunchCtx.)
 hipError_t launch_cast_rays(const RayBatch& b, const RayAccelView& a, hipStream_t s);
 // eray_rays_reach_light: Engine::reaches_light per caller-supplied shadow ray.  `f` carries the
 // triangle records, the descriptors and the object count, the rest zero.

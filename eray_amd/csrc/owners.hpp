@@ -139,6 +139,14 @@ struct RayAccel {
     DeviceBuf<accel::Hot> hot;
     DeviceBuf<uint32_t> index;
     bool valid = false;
+    // counts every event after which a launch plan that holds the arrays' addresses must not be
+    // replayed: a build, a drop (a rebuilding refit does both), eray_scene_add_object and
+    // eray_scene_reset.  Part of the general tracer's plan keys (capi_frames.cpp).  A refit that
+    // keeps the topology rewrites the arrays in place and does not count; nor does
+    // eray_scene_update_object, which only clears `valid` until that refit (meanwhile the tracer's
+    // plans are keyed without a hierarchy).  It outlives drop().
+    uint64_t gen = 0;
+    uint32_t covered = 0;  // objects the last build gave a hierarchy
     // what the last build covered (eray_debug_ray_accel_check): its min_faces, node and slot counts
     uint32_t min_faces = 0;
     size_t node_count = 0, slot_count = 0;
@@ -162,6 +170,8 @@ struct RayAccel {
     }
     void drop() {
         refit.release();
+        ++gen;
+        covered = 0;
         valid = false;
         min_faces = 0;
         node_count = slot_count = 0;

@@ -33,8 +33,8 @@
 // per lane (first_face); objects without a hierarchy keep the tiles, and since the choice is per
 // object (wave- and workgroup-uniform) the tiles' barriers stay uniform.  out_rgb's shadow and
 // reflected rays search the objects that have a hierarchy through it as well: cast.hpp's walk takes
-// a face finder, and rays_accel_kernel passes AccelFaces, which holds the RayAccelView and the
-// lane's stack column (empty again once the primary walk has returned, so the secondary walks
+// a face finder, and rays_accel_kernel passes AccelFaces (accel_faces.hpp, shared with the general
+// tracer), which holds the RayAccelView and the lane's stack column (empty again once the primary walk has returned, so the secondary walks
 // reuse it: no more LDS, no scratch).  Objects without a hierarchy are scanned per lane by those
 // rays — they run inside the walk's divergent loop, where no workgroup barrier can stand.  Same
 // faces, same u, v, t, same colours.
@@ -47,6 +47,7 @@
 // ERAY_RAYS_BRUTE_FORCE is the plain form: every lane walks every face through its own loads
 // (cast.hpp first_face), no tiles, no workgroup-level skips — the same exact_test on the same
 // records, so the same u, v, t bit for bit (tests/test_gpu_rays.py compares the two).
+#include "accel_faces.hpp"
 #include "cast.hpp"
 #include "device_math.hpp"
 #include "hit.hpp"
@@ -192,51 +193,9 @@ __global__ void __launch_bounds__(256) rays_kernel(RayBatch b) {
     }
 }
 
-// The walk's stack of one lane: level k of thread t at s_stack[k][t].
-struct LaneStack {
-    uint32_t* base;
-    uint32_t n;
-    __device__ __forceinline__ void push(uint32_t x) { base[256u * n++] = x; }
-    __device__ __forceinline__ uint32_t pop() { return base[256u * --n]; }
-    __device__ __forceinline__ bool empty() const { return n == 0; }
-};
-
-// An object's first passing face through its hierarchy (accel_walk.hpp) for a ray that passed its
-// box; rays the margin proof does not cover scan per lane.
-__device__ __forceinline__ int accel_object_face(const TriHot* tris, const RayAccelView& a, const accel::Object& ao,
-                                                 const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t,
-                                                 uint32_t* stack) {
-    const float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z};
-    LaneStack st{stack, 0u};
-    const int f = accel::accel_first_face(ao, a.nodes, a.index, of, df, st, [&](uint32_t slot) {
-        const TriHot r = a.hot[slot];
-        float uu, vv, tt;
-        if (!exact_test(r, o, d, uu, vv, tt)) return false;
-        u = uu;
-        v = vv;
-        t = tt;
-        return true;
-    });
-    return f == accel::kAccelFallback ? first_face(tris, ob, o, d, u, v, t, nullptr) : f;
-}
-
-// The face finder (cast.hpp) of out_rgb's shadow and reflected rays in a scene with a hierarchy:
-// an object that has one is searched as the primary ray searches it (the box, the unculled faces,
-// the walk; fallback rays scan), any other by the per-lane scan — these rays run inside the
-// divergent walk of cast.hpp, where the tiles' barriers cannot be reached by the whole workgroup.
-// `stack` is the lane's column of s_stack: the primary walk has returned, so it is empty, and
-// every search leaves it empty again.
-struct AccelFaces {
-    const TriHot* tris;
-    const RayAccelView& a;
-    uint32_t* stack;
-    __device__ __forceinline__ int operator()(uint32_t oi, const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t) const {
-        const accel::Object ao = load_const(&a.objs[oi], 0);
-        if (!ao.has) return first_face(tris, ob, o, d, u, v, t, nullptr);
-        if (!bbox_hit(ob, o, d)) return -1;
-        return accel_object_face(tris, a, ao, ob, o, d, u, v, t, stack);
-    }
-};
+// (LaneStack, accel_object_face and AccelFaces, the finder through the hierarchy: accel_faces.hpp,
+// here with the workgroup-wide stack array's stride of 256.)
+constexpr uint32_t kStackStride = 256;
 
 // rays_kernel's tiled form for a scene with a ray-query hierarchy: objects that have one go
 // through it, the others through the tiles (the choice is per object, so every barrier of
@@ -264,13 +223,13 @@ __global__ void __launch_bounds__(256) rays_accel_kernel(RayBatch b, RayAccelVie
             int f = -1;
             if (ao.has) {  // (workgroup-uniform)
                 if (live && bbox_hit(ob, o, d))
-                    f = accel_object_face(p.tris, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
+                    f = accel_object_face<kStackStride>(p.tris, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
             } else {
                 f = tile_first_face(p.tris, ob, live && bbox_hit(ob, o, d), o, d, u, v, t, s_tile, s_need, phase);
             }
             closer(h, oi, f, u, v, t, o, d, C);
         }
-        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h, AccelFaces{p.tris, a, &s_stack[0][threadIdx.x]});
+        if (live) store_ray<kRgb, kBounce>(b, i, o, d, h, AccelFaces<kStackStride>{p.tris, a, &s_stack[0][threadIdx.x]});
     }
 }
 
@@ -310,7 +269,7 @@ __global__ void __launch_bounds__(256) reach_kernel(ReachBatch b, RayAccelView a
                 const accel::Object ao = load_const(&a.objs[oi], 0);
                 if (ao.has) {  // (workgroup-uniform)
                     tiles = false;
-                    if (inbox) f = accel_object_face(p.tris, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
+                    if (inbox) f = accel_object_face<kStackStride>(p.tris, a, ao, ob, o, d, u, v, t, &s_stack[0][threadIdx.x]);
                 }
             }
             if (tiles) f = tile_first_face(p.tris, ob, inbox, o, d, u, v, t, s_tile, s_need, phase);

@@ -9,7 +9,8 @@
 // sub-block), every ray finds each object's FIRST face whose Triangle::intersects passes
 // (Object::intersects, object.rs:58-81: bbox test, then the faces in index order), with the
 // triangle records read through L1/L2 (TriHot, 48 B) — camera rays from the faces their wave can
-// reach (the background skip below), the others from every face.  It runs only when the caller asks for
+// reach (the background skip below), the others from every face, or, in a scene with a ray-query
+// hierarchy, through it (the Accel pack below).  It runs only when the caller asks for
 // anti_aliasing > 0, or for bounces > 0 on a scene with a reflection output; the reference's
 // default engine never takes it.
 //
@@ -27,6 +28,7 @@
 // keyed by the caller's seed with counter (x, y, sample, 0) — words 0 and 1 are the x and y
 // draws — mapped to [-1, 1) exactly as rand 0.8's UniformFloat::sample_single does.  The
 // oracle uses the same stream (oracle_render_aa), so results are comparable bit for bit.
+#include "accel_faces.hpp"
 #include "cast.hpp"
 #include "cull_record.hpp"
 #include "device_math.hpp"
@@ -249,6 +251,80 @@ __device__ rgb cast_ray(const FrameParams& p, f3 o, f3 d, int32_t* face_out, boo
     return walk<kBounce>(p, L);
 }
 
+// The ray-query hierarchy in the tracer.  trace_kernel and trace_binned_kernel take the scene's
+// hierarchy as an optional second kernel argument (the parameter pack `Accel`: empty, or one
+// RayAccelView; launch_trace passes it when the context hands it one).  With it the shadow and
+// reflected rays find each object's first face through accel_faces.hpp's AccelFaces — the box, the
+// unculled faces, the walk, the per-lane scan for fallback rays and for objects without a hierarchy
+// — i.e. the face and the u, v, t bits of the scan.  The walk's stack is the lane's column of an LDS
+// array [accel::kStackDepth][stride]; every search starts at depth 0 and returns with the stack
+// empty.  Without it (the empty pack) every function below is the code it was before the pack.
+// kCall: the search stands in a function of its own, called, not inlined (cast.hpp's walk holds two
+// searches, reaches_light and surface).  trace_kernel calls it: inlined, its kBounce build needs 230
+// VGPRs and loses the third workgroup per CU that its LDS still allows (154 called).
+// trace_binned_kernel inlines it and stays at three workgroups per CU (168 VGPRs; 35 / 4 VGPRs
+// spilled with / without bounces, against 58 / 58 called and 22 / 0 without a hierarchy): the
+// choices, and the two-workgroup build (248 / 175 VGPRs, no spill), can be built with the macros
+// below for an A/B.
+#ifndef ERAY_TRACE_ACCEL_CALL
+#define ERAY_TRACE_ACCEL_CALL 1
+#endif
+#ifndef ERAY_TRACE_BINNED_ACCEL_CALL
+#define ERAY_TRACE_BINNED_ACCEL_CALL 0
+#endif
+#ifndef ERAY_TRACE_BINNED_ACCEL_WGS
+#define ERAY_TRACE_BINNED_ACCEL_WGS 3
+#endif
+constexpr bool kTraceAccelCall = ERAY_TRACE_ACCEL_CALL != 0, kBinnedAccelCall = ERAY_TRACE_BINNED_ACCEL_CALL != 0;
+constexpr int kBinnedAccelWgs = ERAY_TRACE_BINNED_ACCEL_WGS;
+constexpr uint32_t kStackBytes = accel::kStackDepth * 64u * 4u;  // one wave's stack: [level][lane]
+template <uint32_t kStride>
+__device__ __noinline__ int accel_search(const TriHot* tris, const RayAccelView* a, uint32_t* stack, uint32_t oi,
+                                         const ObjGeom* ob, f3 o, f3 d, float* uvt) {
+    float u = 0.0f, v = 0.0f, t = 0.0f;
+    const int f = AccelFaces<kStride>{tris, *a, stack}(oi, *ob, o, d, u, v, t);
+    uvt[0] = u;
+    uvt[1] = v;
+    uvt[2] = t;
+    return f;
+}
+template <uint32_t kStride, bool kCall>
+struct TraceAccelFaces {
+    const TriHot* tris;
+    const RayAccelView& a;
+    uint32_t* stack;
+    __device__ __forceinline__ int operator()(uint32_t oi, const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t) const {
+        if constexpr (kCall) {
+            float uvt[3];
+            const int f = accel_search<kStride>(tris, &a, stack, oi, &ob, o, d, uvt);
+            u = uvt[0];
+            v = uvt[1];
+            t = uvt[2];
+            return f;
+        } else {
+            return AccelFaces<kStride>{tris, a, stack}(oi, ob, o, d, u, v, t);
+        }
+    }
+};
+// trace_kernel's camera rays with a hierarchy: the wave's live faces where the scene has culling
+// records (at most kSkipTris faces), else the same finder as the other rays (the same call).
+template <class Find>
+struct LiveOr {
+    const TriHot* tris;
+    const uint64_t* live;  // wave-uniform
+    const Find& find;
+    __device__ __forceinline__ int operator()(uint32_t oi, const ObjGeom& ob, f3 o, f3 d, float& u, float& v, float& t) const {
+        return live ? first_face(tris, ob, o, d, u, v, t, live) : find(oi, ob, o, d, u, v, t);
+    }
+};
+// cast_ray with finders: `cam` searches the first level (the camera ray), `find` the others.
+template <bool kBounce, class CamFind, class Find>
+__device__ rgb cast_ray(const FrameParams& p, f3 o, f3 d, int32_t* face_out, const CamFind& cam, const Find& find) {
+    Level L;
+    if (!surface(p, o, d, L, face_out, cam)) return miss_color();
+    return walk<kBounce>(p, L, find);
+}
+
 // Element r of a per-ray array (r < kRays, run time) without a dynamically indexed private array
 // (which would live in scratch memory).
 template <typename T>
@@ -336,10 +412,10 @@ __device__ __forceinline__ void store_pixel(const FrameParams& p, uint32_t px, u
 
 // The binned search of a sub-block's rays (camera_hits: the wave alone, or with `heavy` the
 // workgroup's four waves together) and, in the pixel's lane of wave 0, the walks of their hits:
-// the pixel's sum and first face.
-template <bool kBounce, bool heavy>
+// the pixel's sum and first face.  `find`: nothing (the walks scan), or the walks' face finder.
+template <bool kBounce, bool heavy, class... Find>
 __device__ void binned_pixel(const FrameParams& p, uint32_t px, uint32_t y, bool valid, uint32_t bin,
-                             unsigned char* lds, rgb& avg, int32_t& face) {
+                             unsigned char* lds, rgb& avg, int32_t& face, const Find&... find) {
     const bool lead = !heavy || (threadIdx.x >> 6) == 0;
     const f3 C = mk3(p.cx, p.cy, p.cz);
     const uint32_t n = 1 + p.aa;
@@ -359,7 +435,7 @@ __device__ void binned_pixel(const FrameParams& p, uint32_t px, uint32_t y, bool
             if (hr.f >= 0) {
                 Level L;
                 fill_level(p, C, pick(d, r), hr, L);
-                c = walk<kBounce>(p, L);
+                c = walk<kBounce>(p, L, find...);
             }
             if (i0 + r == 0) {
                 avg = c;
@@ -376,8 +452,8 @@ __device__ void binned_pixel(const FrameParams& p, uint32_t px, uint32_t y, bool
 // tracer setup's detail list puts those first, bins.hip) would keep its wave long after the
 // others; trace_binned_kernel's first workgroups take them instead, the whole workgroup on one
 // sub-block (camera_hits<4>).
-template <bool kBounce>
-__device__ void heavy_role(const FrameParams& p, unsigned char* s_raw, uint32_t first, uint32_t stride) {
+template <bool kBounce, class... Find>
+__device__ void heavy_role(const FrameParams& p, unsigned char* s_raw, uint32_t first, uint32_t stride, const Find&... find) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t nheavy = *p.detail_heavy;
     for (uint32_t hv = first; hv < nheavy; hv += stride) {
@@ -389,14 +465,17 @@ __device__ void heavy_role(const FrameParams& p, unsigned char* s_raw, uint32_t 
         const bool valid = px < p.cam_w && py < p.rows;
         rgb avg{0.0f, 0.0f, 0.0f};
         int32_t face = -1;
-        binned_pixel<kBounce, true>(p, px, y, valid, bin, s_raw, avg, face);
+        binned_pixel<kBounce, true>(p, px, y, valid, bin, s_raw, avg, face, find...);
         if (wave == 0 && valid) store_pixel(p, px, py, avg, face);
         __syncthreads();  // (the next sub-block rewrites the group's LDS)
     }
 }
 
-template <bool kBounce>
-__global__ void __launch_bounds__(256) trace_kernel(FrameParams p) {
+// With a hierarchy (Accel): the workgroup's stack array [level][thread] beside the culling records
+// (32 KB more LDS: three workgroups per CU resident instead of four); the camera rays of a wave
+// without a live mask use the same finder.
+template <bool kBounce, class... Accel>
+__global__ void __launch_bounds__(256) trace_kernel(FrameParams p, Accel... a) {
     __shared__ TriCull s_cull[kSkipTris];  // the culling records (scenes of at most kSkipTris faces)
     __shared__ uint64_t s_live[4][kSkipTris / 64];  // each wave's live_mask (LDS: run-time indexed)
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -436,6 +515,13 @@ __global__ void __launch_bounds__(256) trace_kernel(FrameParams p) {
     if (skip) {  // every camera ray misses (the jitter only moves a ray that misses anyway)
         avg = miss_color();
         for (uint32_t s = 0; s < p.aa; ++s) avg = cadd(avg, miss_color());
+    } else if constexpr (sizeof...(Accel) != 0) {
+        __shared__ uint32_t s_stack[accel::kStackDepth][256];
+        const TraceAccelFaces<256, kTraceAccelCall> find{p.tris, a..., &s_stack[0][threadIdx.x]};
+        const LiveOr<TraceAccelFaces<256, kTraceAccelCall>> cam{p.tris, live, find};
+        avg = cast_ray<kBounce>(p, C, pixel_ray(p, px, y, 0), &face, cam, find);
+        for (uint32_t s = 0; s < p.aa; ++s)
+            avg = cadd(avg, cast_ray<kBounce>(p, C, pixel_ray(p, px, y, 1 + s), nullptr, cam, find));
     } else {
         avg = cast_ray<kBounce>(p, C, pixel_ray(p, px, y, 0), &face, false, live);
         for (uint32_t s = 0; s < p.aa; ++s)
@@ -521,14 +607,27 @@ __device__ void fill_color(const FrameParams& p, uint32_t x0, uint32_t py0, uint
 // Three workgroups per CU (168 VGPRs, a few spilled; LDS 45 KB each): 3840x2160 / 70k with
 // AA = 4 178 -> 130 us per frame against two per CU (178 VGPRs), same-box A/B
 // (profiles/r04/ab/ab_r04f.txt).
-template <bool kBounce>
-__global__ void __launch_bounds__(256, 3) trace_binned_kernel(FrameParams p) {
+// With a hierarchy (Accel) the walk's stacks (one wave's: kStackBytes, row length 64) live inside
+// the same LDS bytes:
+//  * light role — the wave's own BinGroup<1>: camera_hits<1> ends with a wave_sync and nothing reads
+//    the group again before the next camera_hits<1> of the same wave, which the wave enters only
+//    once its lanes have left the walks (binned_pixel's i0 loop is wave-uniform, and a wave's LDS
+//    accesses complete in program order); no other wave ever touches these bytes.
+//  * heavy role — the bytes BEHIND BinGroup<4>, not inside it: only wave 0 walks, while waves 1-3 run
+//    ahead into the next camera_hits<4> (binned_pixel's next pass, or heavy_role's next sub-block)
+//    and write E[wave] and R there before its first barrier.  They write inside BinGroup<4> only,
+//    so wave 0's stack stands where no wave writes at all, and no barrier had to be added.
+template <bool kBounce, class... Accel>
+__global__ void __launch_bounds__(256, sizeof...(Accel) ? kBinnedAccelWgs : 3) trace_binned_kernel(FrameParams p, Accel... a) {
     constexpr size_t kLds = 4 * sizeof(BinGroup<1>) > sizeof(BinGroup<4>) ? 4 * sizeof(BinGroup<1>) : sizeof(BinGroup<4>);
+    static_assert(sizeof(BinGroup<1>) >= kStackBytes && sizeof(BinGroup<1>) % 4 == 0, "light role: the stack fits the wave's group");
+    static_assert(sizeof(BinGroup<4>) % 4 == 0 && sizeof(BinGroup<4>) + kStackBytes <= kLds, "heavy role: the stack fits behind the group");
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kLds];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t nheavy_wgs = p.trace_heavy_wgs, nfill = p.trace_fill_wgs;
     if (blockIdx.x < nheavy_wgs) {  // workgroup-uniform: the heavy sub-blocks, a workgroup each
-        heavy_role<kBounce>(p, s_raw, blockIdx.x, nheavy_wgs);
+        heavy_role<kBounce>(p, s_raw, blockIdx.x, nheavy_wgs,
+                            TraceAccelFaces<64, kBinnedAccelCall>{p.tris, a, reinterpret_cast<uint32_t*>(s_raw + sizeof(BinGroup<4>)) + lane}...);
         return;
     }
     const uint32_t wg = blockIdx.x - nheavy_wgs;
@@ -565,7 +664,8 @@ __global__ void __launch_bounds__(256, 3) trace_binned_kernel(FrameParams p) {
         const bool valid = px < p.cam_w && py < p.rows;
         rgb avg{0.0f, 0.0f, 0.0f};
         int32_t face = -1;
-        binned_pixel<kBounce, false>(p, px, y, valid, bin, s_raw + wave * sizeof(BinGroup<1>), avg, face);
+        binned_pixel<kBounce, false>(p, px, y, valid, bin, s_raw + wave * sizeof(BinGroup<1>), avg, face,
+                                     TraceAccelFaces<64, kBinnedAccelCall>{p.tris, a, reinterpret_cast<uint32_t*>(s_raw + wave * sizeof(BinGroup<1>)) + lane}...);
         if (valid) store_pixel(p, px, py, avg, face);
     }
 }
@@ -579,8 +679,9 @@ hipError_t launch_trace_cull(const FrameParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_trace(const FrameParams& p0, const LaunchCtx&, hipStream_t s) {
+hipError_t launch_trace(const FrameParams& p0, const LaunchCtx& lc, hipStream_t s) {
     FrameParams p = p0;
+    const RayAccelView& a = lc.accel;  // objs null: every ray scans (capi_frames.cpp prepare_render)
     if (p.trace_bins) {  // listed sub-blocks: heavy, light and background roles
         if (!p.detail_list || !p.detail_heavy || !p.detail_occ) return hipErrorInvalidValue;
         static const uint32_t cus = [] {
@@ -597,13 +698,17 @@ hipError_t launch_trace(const FrameParams& p0, const LaunchCtx&, hipStream_t s) 
         // AA = 4 129 -> 111 us against two per CU, profiles/r04/ab/ab_r04k.txt)
         p.trace_light_wgs = 8 * cus;
         const dim3 grid(p.trace_heavy_wgs + p.trace_fill_wgs + p.trace_light_wgs);
-        if (p.bounces) hipLaunchKernelGGL(trace_binned_kernel<true>, grid, dim3(256), 0, s, p);
+        if (a.objs && p.bounces) hipLaunchKernelGGL((trace_binned_kernel<true, RayAccelView>), grid, dim3(256), 0, s, p, a);
+        else if (a.objs) hipLaunchKernelGGL((trace_binned_kernel<false, RayAccelView>), grid, dim3(256), 0, s, p, a);
+        else if (p.bounces) hipLaunchKernelGGL(trace_binned_kernel<true>, grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL(trace_binned_kernel<false>, grid, dim3(256), 0, s, p);
         return hipGetLastError();
     }
     if (p.trace_cull && p.total_tris > kSkipTris) return hipErrorInvalidValue;
     const dim3 grid(((p.cam_w + 63) / 64) * ((p.rows + 3) / 4));
-    if (p.bounces) hipLaunchKernelGGL(trace_kernel<true>, grid, dim3(256), 0, s, p);
+    if (a.objs && p.bounces) hipLaunchKernelGGL((trace_kernel<true, RayAccelView>), grid, dim3(256), 0, s, p, a);
+    else if (a.objs) hipLaunchKernelGGL((trace_kernel<false, RayAccelView>), grid, dim3(256), 0, s, p, a);
+    else if (p.bounces) hipLaunchKernelGGL(trace_kernel<true>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(trace_kernel<false>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }

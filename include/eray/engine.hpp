@@ -160,6 +160,9 @@ public:
     // refittable (the three-argument form; false in the other) is the host build with what a refit needs kept beside it
     // (eray_scene_build_ray_accel_refittable): refit_ray_accel then keeps this tree's topology.  With
     // on_device it is a failure (ERAY_E_INVALID_ARGUMENT): a device build is always refittable.
+    // The hierarchy also speeds up render(): with anti-aliasing or bounces the shadow and reflected
+    // rays of every pixel search the covered objects through it (ERAY_HAS_TRACE_RAY_ACCEL; the same
+    // image, bit for bit) — what pays for objects whose bounding box is real, i.e. lets those rays in.
     struct RayAccelInfo {
         uint32_t objects, max_depth;
         uint64_t nodes, faces, unculled_faces, device_bytes;

@@ -274,6 +274,24 @@ typedef struct eray_render_params {
 #define ERAY_RENDER_SHARED_DETAIL 32u    /* binned meshes: every detail sub-block's search shared by its
                                             workgroup (default: only the heavy ones; the light ones
                                             search their own bins without workgroup barriers)     */
+/* The general tracer (anti_aliasing > 0, or bounces > 0 on a reflective scene) and the ray-query
+ * hierarchy (eray_scene_build_ray_accel and its kin, below).  In builds that define
+ * ERAY_HAS_TRACE_RAY_ACCEL, a scene with a valid hierarchy is rendered with it: the shadow and
+ * reflected rays of every pixel find the first face of each covered object through the hierarchy
+ * (the box, the unculled faces, the walk; rays the margin proof does not cover, and objects
+ * without a hierarchy, scan as before) instead of scanning every face of every object whose box
+ * they pass — the same frame, bit for bit (RGB, PPM bytes, faces).  Camera rays keep their own
+ * search (culling records, screen bins); where they have neither they use the hierarchy too.  The
+ * hierarchy form is taken when the render is the general tracer's, the hierarchy is valid and
+ * covers an object whose bounding box is not a point in x and y (the reference's loaded meshes
+ * carry a (0,0,0) box that rejects almost every such ray: nothing to gain there), and neither
+ * ERAY_RENDER_BRUTE_FORCE nor ERAY_RENDER_NO_RAY_ACCEL is set.  ERAY_RENDER_NO_RAY_ACCEL makes the
+ * general tracer ignore the hierarchy (the A/B form: the per-ray scan); the frame kernel, which
+ * has no such rays, ignores the flag.  The launch plans of eray_render_frames / eray_render_prepare
+ * are keyed with the hierarchy's addresses and generation: a build, a drop, a geometry change or a
+ * rebuilding refit gets a new plan, a refit in place keeps the plan. */
+#define ERAY_RENDER_NO_RAY_ACCEL 64u
+#define ERAY_HAS_TRACE_RAY_ACCEL 1
 
 int eray_render(eray_ctx* ctx, const eray_render_params* params);
 /* Renders `frames` frames back to back with the same parameters (a serving / animation loop

@@ -102,6 +102,12 @@ int eray_debug_ray_accel_arrays(eray_ctx* ctx, uint32_t which, void* out, size_t
  * launch (on != 0, the default) or every level in a launch of its own; the bytes written are the
  * same.  Read when the call enqueues, so a captured graph keeps the form it was captured with. */
 int eray_debug_set_refit_top_levels(eray_ctx* ctx, int on);
+/* How many objects the last general-tracer render call (eray_render, eray_render_frames,
+ * eray_render_prepare, each frame of eray_render_camera_path with anti-aliasing or bounces) searched
+ * through the ray-query hierarchy (ERAY_HAS_TRACE_RAY_ACCEL): the objects the hierarchy covers, or 0
+ * when its shadow and reflected rays scanned.  Decided on the host when the call enqueues; no device
+ * round trip.  Frame-kernel renders leave it as it was. */
+int eray_debug_trace_ray_accel(eray_ctx* ctx, uint32_t* objects);
 
 #ifdef __cplusplus
 }
