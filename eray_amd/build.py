@@ -25,7 +25,7 @@ LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "liberay_hip.so")
 
 SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "capi_setup.cpp",
-           "capi_frames.cpp", "capi_rays.cpp", "comm.cpp", "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
+           "capi_frames.cpp", "capi_rays.cpp", "comm.cpp", "gather_debug.cpp", "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
             f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),
@@ -112,13 +112,17 @@ REFIT_HOSTTREE_MAIN = os.path.join(TESTS_CPP, "accel_refit_hosttree_main.cpp")
 # tests/cpp/update_args_main.cpp (headers only)
 UPDATE_ARGS_MAIN = os.path.join(TESTS_CPP, "update_args_main.cpp")
 UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "include", "eray_hip.h")]
+# tests/cpp/gather_plan_main.cpp (headers only): the multi-GPU gather's planning
+GATHER_PLAN_MAIN = os.path.join(TESTS_CPP, "gather_plan_main.cpp")
+GATHER_PLAN_HEADERS = [os.path.join(CSRC, "gather_plan.hpp"), os.path.join(CSRC, "band_rows.hpp"),
+                       os.path.join(ROOT, "include", "eray_hip.h")]
 
 
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
     the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
     test_refit_hosttree, accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_hosttree_main, accel_refit_async_main,
-    update_args_main).  Plain g++: the
+    update_args_main, gather_plan_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -179,6 +183,10 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     exe = os.path.join(BIN_DIR, "update_args_main")
     if force or not _newer(exe, [UPDATE_ARGS_MAIN, *UPDATE_ARGS_HEADERS]):
         run([cxx, "-std=c++17", "-O2", "-Wall", UPDATE_ARGS_MAIN, "-o", exe])
+    outs.append(exe)
+    exe = os.path.join(BIN_DIR, "gather_plan_main")
+    if force or not _newer(exe, [GATHER_PLAN_MAIN, *GATHER_PLAN_HEADERS]):
+        run([cxx, "-std=c++17", "-O2", "-Wall", GATHER_PLAN_MAIN, "-o", exe])
     outs.append(exe)
     return outs
 

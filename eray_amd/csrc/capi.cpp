@@ -1,5 +1,5 @@
 // capi.cpp — implementation of include/eray_hip.h: context, device memory, the shaderlib node entry
-// points, the scene API with its upload, PPM packing and the eray_internal_* / eray_debug_* hooks.
+// points, the scene API with its upload, PPM packing, eray_internal_error and the eray_debug_* hooks.
 // The frame path is capi_setup.cpp (camera setup, bins, frame tags) and capi_frames.cpp (the
 // eray_render* and eray_time_* entry points); the ray queries and their hierarchy capi_rays.cpp — all
 // on the same context, ctx.hpp.  Host code only; the kernels live in render.hip and shaderlib.hip.
@@ -682,107 +682,8 @@ int eray_ppm_header(uint32_t w, uint32_t h, char* buf, size_t cap, size_t* len) 
 
 }  // extern "C"
 
-// The source of the n frames local + k * stride (k < n) as this context last rendered them
-// (tag_frames); every frame must have the same one.
-int eray_internal_frame_source(eray_ctx* ctx, const uint8_t* local, uint64_t stride, uint32_t n, FrameSource* out) {
-    if (!ctx || !out) return ERAY_E_INVALID_ARGUMENT;
-    *out = FrameSource{};
-    for (uint32_t k = 0; k < n; ++k) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(local) + (uintptr_t)(k * stride);
-        const eray_ctx::SlotTag* t = nullptr;
-        for (auto it = ctx->slot_tags.rbegin(); it != ctx->slot_tags.rend(); ++it)
-            if (it->ppm == a) {
-                t = &*it;
-                break;
-            }
-        if (!t)
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "gather: frame %u at %p was not rendered by this context", k,
-                             (const void*)a);
-        if (k == 0) {
-            *out = t->src;
-        } else if (t->src.kind != out->kind || t->src.key != out->key) {
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "gather: frames 0 and %u come from different renders", k);
-        }
-    }
-    if (out->kind == kSrcOther)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                         "gather: the frames were rendered with anti-aliasing, bounces or brute force (no pixel rectangles)");
-    return ERAY_OK;
-}
-
-// The pixel rectangles of `src` (waits for their host copy): the last scene-camera setup when it
-// is src's (same camera, scene and rows), or the union of camera path src.key's cameras while it
-// is among the last kUnionRing paths.
-int eray_internal_source_layout(eray_ctx* ctx, const FrameSource& src, SceneLayout* out) {
-    if (!ctx || !out) return ERAY_E_INVALID_ARGUMENT;
-    auto same_rows = [](const FrameSource& a, const FrameSource& b) {
-        return a.W == b.W && a.H == b.H && a.row0 == b.row0 && a.rows == b.rows && a.band_shift == b.band_shift &&
-               a.band_stride == b.band_stride;
-    };
-    out->src = src;
-    out->rects.clear();
-    const size_t nobj = ctx->objects.size();
-    if (src.kind == kSrcScene) {
-        const FrameSource& s = ctx->setup_src;
-        if (s.kind != kSrcScene || s.key != src.key || !same_rows(s, src))
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                             "gather: the scene camera's last setup is not the one these frames were rendered with");
-        if (ctx->state_pending) {
-            HIP_TRY(ctx, hipEventSynchronize(ctx->state_ev));
-            state_arrived(ctx);
-        }
-        for (size_t i = 0; i < nobj; ++i) {
-            const int32_t* r = ctx->h_objs_state[i].g.rect;
-            out->rects.push_back({r[0], r[1], r[2], r[3]});
-        }
-        return ERAY_OK;
-    }
-    if (src.kind == kSrcPath) {
-        const uint32_t e = (uint32_t)(src.key % kUnionRing);
-        if (ctx->union_seq[e] != src.key || !same_rows(ctx->union_src[e], src))
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                             "gather: these camera-path frames are older than the last %u paths", kUnionRing);
-        // (the union covers the objects of the scene the path was rendered from; a scene change
-        // since makes the path's frames ungatherable, as their objects no longer exist)
-        if (ctx->union_nobj[e] != nobj || ctx->union_gen[e] != ctx->scene_gen || nobj > ctx->union_cap())
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                             "gather: the scene changed after these camera-path frames were rendered");
-        HIP_TRY(ctx, hipEventSynchronize(ctx->union_ev[e]));
-        const int32_t* u = ctx->h_union + (size_t)e * 4 * ctx->union_cap();
-        for (size_t i = 0; i < nobj; ++i)
-            out->rects.push_back({u[2 * i], u[2 * nobj + 2 * i], u[2 * i + 1], u[2 * nobj + 2 * i + 1]});
-        return ERAY_OK;
-    }
-    return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "gather: frames of an unknown source");
-}
-// The source of the scene camera's last setup (diagnostics: eray_debug_scene_gather).
-int eray_internal_scene_setup_source(eray_ctx* ctx, FrameSource* out) {
-    if (!ctx || !out) return ERAY_E_INVALID_ARGUMENT;
-    if (ctx->setup_src.kind != kSrcScene)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "no setup of the scene camera: render it first");
-    *out = ctx->setup_src;
-    return ERAY_OK;
-}
-// The context's latest render of the scene camera or of a camera path (kind kSrcNone: none yet).
-void eray_internal_gather_source(const eray_ctx* ctx, FrameSource* out) { *out = ctx->gather_src; }
-// The context's collective scratch block (kCollScratchBytes of device memory, made with it).
-uint8_t* eray_internal_coll_scratch(eray_ctx* ctx) { return ctx->d_coll; }
-void** eray_internal_gather_plan(eray_ctx* ctx, void (*free_fn)(void*)) {
-    ctx->gather_plan_free = free_fn;
-    return &ctx->gather_plan;
-}
-int eray_internal_use_device(eray_ctx* ctx) { return use_device(ctx); }
-
-// Error reporting and the gather's staging buffer for the other translation units (comm.cpp).
+// Error reporting for objload.cpp, which is HIP-free and cannot see ctx.hpp.
 int eray_internal_error(eray_ctx* ctx, int code, const char* msg) { return set_error(ctx, code, "%s", msg); }
-void eray_internal_untag(eray_ctx* ctx, const void* p, size_t bytes) {
-    if (ctx && p) untag_range(ctx, reinterpret_cast<uintptr_t>(p), bytes);
-}
-void* eray_internal_staging(eray_ctx* ctx, size_t bytes) {
-    if (!ctx) return nullptr;
-    if (ctx->d_staging.ensure(ctx, bytes)) return nullptr;
-    return ctx->d_staging;
-}
 
 // Diagnostics (not part of include/eray_hip.h): the screen bins of object `index` as built for
 // the last setup — out[0] bins, out[1] entries, out[2] (face, pixel) pairs (mask bits),

@@ -3,7 +3,7 @@
 // asks about), the screen bins' buffers, and the camera setups of setup.hip / bins.hip — one
 // camera's (enqueue_setup), a path chunk's cameras at once (ensure_multi, enqueue_multi_setup) and
 // the scene camera's with its host copy (sync_setup, state_arrived).  capi_frames.cpp renders with
-// them; capi.cpp's memory calls and eray_internal_* hooks use the tags.  Host code only.
+// them; capi.cpp's memory calls and comm.cpp's gather use the tags.  Host code only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

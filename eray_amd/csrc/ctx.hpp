@@ -1,16 +1,17 @@
 // ctx.hpp — the context behind include/eray_hip.h's eray_ctx handle and what the C-ABI translation
-// units share to work on it: capi.cpp (context, memory, shaderlib nodes, scene, the eray_internal_*
-// and eray_debug_* hooks), capi_setup.cpp (camera setup, bins, frame tags), capi_frames.cpp (the
-// frame entry points) and capi_rays.cpp (ray queries and their hierarchy).  Here: the error policy
-// (set_error, HIP_TRY, use_device), the scene upload, and what the other units need of
-// capi_setup.cpp — declared here and nowhere else.  Private to those four files; comm.cpp and
-// objload.cpp reach the context through internal.hpp's eray_internal_*.
+// units share to work on it: capi.cpp (context, memory, shaderlib nodes, scene, the eray_debug_*
+// hooks), capi_setup.cpp (camera setup, bins, frame tags), capi_frames.cpp (the frame entry
+// points), capi_rays.cpp (ray queries and their hierarchy) and comm.cpp (the multi-GPU gather).
+// Here: the error policy (set_error, HIP_TRY, use_device), the scene upload, and what the other
+// units need of capi_setup.cpp — declared here and nowhere else.  Private to those five files; the
+// HIP-free units report errors without it (objload.cpp through capi.cpp's eray_internal_error).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -39,6 +40,10 @@ struct HostObject {
 
 // Node types of the shaderlib outputs: wave's is IValue, rgb / flat_color / mix_color's IColor.
 inline bool texel_is_color(uint32_t kind) { return kind != ERAY_TEXEL_WAVE; }
+
+// eray_gather_frames' plan: comm.cpp defines it, and how it is deleted.
+struct GatherPlan;
+struct GatherPlanDelete { void operator()(GatherPlan* P) const; };
 
 }  // namespace gpu
 }  // namespace eray
@@ -111,9 +116,8 @@ struct eray_ctx {
     uint32_t union_nobj[kUnionRing] = {};  // objects and scene generation the entry's union covers
     uint64_t union_gen[kUnionRing] = {};
     Event union_ev[kUnionRing];
-    // eray_gather_frames' plan (comm.cpp owns it)
-    void* gather_plan = nullptr;
-    void (*gather_plan_free)(void*) = nullptr;
+    // eray_gather_frames' plan (comm.cpp makes it on the first scene-camera gather)
+    std::unique_ptr<GatherPlan, GatherPlanDelete> gather_plan;
     DeviceBuf<uint32_t> d_acc;    // setup counter, partials and rectangle accumulators (enqueue_setup)
     DeviceBuf<uint32_t> d_begin;  // obj_begin | objkey
     DeviceBuf<int4> d_range;      // binned faces' bin rectangles, areas, binned-object index
@@ -176,7 +180,7 @@ struct eray_ctx {
         (void)hipSetDevice(device);
         for (hipStream_t s : {stream, (hipStream_t)own_stream, (hipStream_t)mc_stream})
             if (s) (void)hipStreamSynchronize(s);
-        if (gather_plan && gather_plan_free) gather_plan_free(gather_plan);  // (while the streams exist)
+        gather_plan.reset();  // (while the streams exist)
         bins_free(bins);
         for (auto& m : mc) bins_free(m.bins);
     }

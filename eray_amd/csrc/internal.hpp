@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "accel_walk.hpp"
+#include "band_rows.hpp"
 
 namespace eray {
 namespace gpu {
@@ -98,11 +99,10 @@ constexpr uint32_t kMaxFramesPerLaunch = 64;
 // that needs more overflows: its objects are scanned through LDS tiles, still exact).
 constexpr uint64_t kMaxSceneTris = (1ull << 26) - 1;
 constexpr size_t kMaxBinEntries = (size_t)1 << 26;
-// The multi-GPU gathers (comm.cpp) serve at most this many ranks, and every buffer a rank needs
-// to take part in their status exchanges (status and count words, the plan records, the plan's
-// rank table) lives in a scratch block allocated with the context — so no rank can fail to enter
-// a collective its peers have entered for want of memory.
-constexpr int kMaxGatherRanks = 64;
+// The multi-GPU gathers (comm.cpp) serve at most 64 ranks (gather_plan.hpp), and every buffer a rank
+// needs to take part in their status exchanges (status and count words, the plan records, the
+// plan's rank table) lives in a scratch block allocated with the context — so no rank can fail to
+// enter a collective its peers have entered for want of memory.
 constexpr size_t kCollScratchBytes = 32u << 10;
 // The MI355X Infinity Cache (the die's last-level cache, MI355X_MICROARCH.md).
 constexpr uint64_t kInfinityCacheBytes = 256ull << 20;
@@ -260,34 +260,6 @@ struct FrameParams {
     // Infinity Cache — the frame's lines then do not evict what the detail waves read back)
     uint32_t store_nt;
 };
-
-// Camera row of rank-local row j (FrameParams::band_shift; shifts and masks: no division in the
-// kernels' per-pixel paths).
-__host__ __device__ inline uint32_t band_camera_row(uint32_t row0, uint32_t band_shift, uint32_t band_mask,
-                                                    uint32_t band_stride, uint32_t j) {
-    return row0 + (j >> band_shift) * band_stride + (j & band_mask);
-}
-// The rank-local rows [*lo, *hi] whose camera rows lie in [y0, y1] (empty: *lo > *hi); the
-// mapping is monotonic, so a camera row range is a local row range.
-__host__ __device__ inline void band_local_range(uint32_t row0, uint32_t band_shift, uint32_t band_stride, int32_t y0,
-                                                 int32_t y1, int32_t* lo, int32_t* hi) {
-    if (band_shift >= 31) {
-        *lo = y0 - (int32_t)row0;
-        *hi = y1 - (int32_t)row0;
-        return;
-    }
-    const int64_t B = (int64_t)1 << band_shift, S = band_stride, off = row0;
-    auto floordiv = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
-    // first local row at or after camera row y0
-    int64_t i = floordiv((int64_t)y0 - off, S), w = (int64_t)y0 - off - i * S;
-    const int64_t l0 = w < B ? i * B + w : (i + 1) * B;
-    // last local row at or before camera row y1
-    i = floordiv((int64_t)y1 - off, S);
-    w = (int64_t)y1 - off - i * S;
-    const int64_t l1 = w < B ? i * B + w : i * B + B - 1;
-    *lo = (int32_t)(l0 < -1 ? -1 : (l0 > 0x7fffffff ? 0x7fffffff : l0));
-    *hi = (int32_t)(l1 < -1 ? -1 : (l1 > 0x7fffffff ? 0x7fffffff : l1));
-}
 
 // Byte offsets of the LDS scene copy: [ObjectDesc x nobj | LightDesc x nl | TriCull x n (if
 // culling) | TriHot x n | TriShade x n]; every section is a whole number of 16-B words.
@@ -529,7 +501,7 @@ void bins_free(BinBuffers& b);
 hipError_t launch_bins_build(const SetupParams& sp, BinBuffers& b, uint32_t tiles_x, bool ordered, hipStream_t s);
 hipError_t launch_pack_ppm(const float* rgb, uint32_t w, uint32_t h, uint8_t* out, hipStream_t s);
 
-// ------------------------------------------------------------- capi.cpp internals for comm.cpp
+// ----------------------------------------------------------------- frame sources (the gather's)
 // Where a frame in an output buffer came from (eray_gather_frames' scene-camera transport): the
 // context tags every PPM output slot it renders into with the render's kind and key.  kind
 // kSrcScene: a frame kernel render of the scene camera, key = a hash of (camera, scene
