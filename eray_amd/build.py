@@ -116,13 +116,16 @@ UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "
 GATHER_PLAN_MAIN = os.path.join(TESTS_CPP, "gather_plan_main.cpp")
 GATHER_PLAN_HEADERS = [os.path.join(CSRC, "gather_plan.hpp"), os.path.join(CSRC, "band_rows.hpp"),
                        os.path.join(ROOT, "include", "eray_hip.h")]
+# tests/cpp/bin_layout_main.cpp (headers only): the screen bins' sizing
+BIN_LAYOUT_MAIN = os.path.join(TESTS_CPP, "bin_layout_main.cpp")
+BIN_LAYOUT_HEADERS = [os.path.join(CSRC, "bin_layout.hpp"), os.path.join(CSRC, "band_rows.hpp")]
 
 
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
     the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
     test_refit_hosttree, accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_hosttree_main, accel_refit_async_main,
-    update_args_main, gather_plan_main).  Plain g++: the
+    update_args_main, gather_plan_main, bin_layout_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -188,6 +191,13 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     if force or not _newer(exe, [GATHER_PLAN_MAIN, *GATHER_PLAN_HEADERS]):
         run([cxx, "-std=c++17", "-O2", "-Wall", GATHER_PLAN_MAIN, "-o", exe])
     outs.append(exe)
+    # (only where the program's source is there: a tests/ directory older than bin_layout.hpp still
+    # gets everything it runs; tests/test_bin_layout.py fails without the program)
+    if os.path.exists(BIN_LAYOUT_MAIN):
+        exe = os.path.join(BIN_DIR, "bin_layout_main")
+        if force or not _newer(exe, [BIN_LAYOUT_MAIN, *BIN_LAYOUT_HEADERS]):
+            run([cxx, "-std=c++17", "-O2", "-Wall", BIN_LAYOUT_MAIN, "-o", exe])
+        outs.append(exe)
     return outs
 
 

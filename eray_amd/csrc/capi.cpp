@@ -696,8 +696,7 @@ extern "C" int eray_debug_bin_stats(eray_ctx* ctx, uint32_t index, uint64_t* out
     if (!ctx || !out || index >= ctx->objects.size() || ctx->objects[index].T <= kDirectMax || !ctx->bins.start)
         return ERAY_E_INVALID_ARGUMENT;
     const BinBuffers& b = ctx->bins;
-    uint32_t k = 0;
-    for (uint32_t i = 0; i < index; ++i) k += ctx->objects[i].T > kDirectMax;
+    const uint32_t k = binned_before(ctx, index);
     std::vector<uint32_t> start(b.nbins + 1);
     ObjectDesc d{};
     if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
@@ -749,8 +748,7 @@ extern "C" int eray_debug_bin_entries(eray_ctx* ctx, uint32_t index, uint32_t bi
         bin >= ctx->bins.nbins)
         return ERAY_E_INVALID_ARGUMENT;
     const BinBuffers& b = ctx->bins;
-    uint32_t k = 0;
-    for (uint32_t i = 0; i < index; ++i) k += ctx->objects[i].T > kDirectMax;
+    const uint32_t k = binned_before(ctx, index);
     uint32_t se[2];
     if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
         hipMemcpy(se, b.start + (size_t)k * b.nbins + bin, 8, hipMemcpyDeviceToHost) != hipSuccess)
@@ -780,8 +778,7 @@ extern "C" int eray_debug_bin_counts(eray_ctx* ctx, uint32_t index, uint32_t* co
     if (!ctx || !nbins || index >= ctx->objects.size() || ctx->objects[index].T <= kDirectMax || !ctx->bins.start)
         return ERAY_E_INVALID_ARGUMENT;
     const BinBuffers& b = ctx->bins;
-    uint32_t k = 0;
-    for (uint32_t i = 0; i < index; ++i) k += ctx->objects[i].T > kDirectMax;
+    const uint32_t k = binned_before(ctx, index);
     *nbins = b.nbins;
     const uint32_t m = std::min(b.nbins, cap);
     std::vector<uint32_t> st((size_t)m + 1);

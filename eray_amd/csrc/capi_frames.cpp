@@ -125,9 +125,9 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     p.lds_scene = (ctx->total_tris <= kCacheTris && p.nobj <= kCacheObjects && p.nlights <= kCacheLights) ? 1u : 0u;
     p.spec_pow = ctx->spec_pow ? 1u : 0u;
     p.example_mat = ctx->example_mat ? 1u : 0u;
-    p.tiles_x = (W + 63) / 64;
-    p.bins_x = (W + kBinW - 1) / kBinW;
-    p.bin_phase = rp->row0 % kBinH;
+    p.tiles_x = frame_tiles_x(W);
+    p.bins_x = bin_cols(W);
+    p.bin_phase = bin_phase(rp->row0);
     p.aa = rp->anti_aliasing;
     p.bounces = bounces;
     p.seed_lo = (uint32_t)rp->aa_seed;
@@ -786,7 +786,7 @@ struct BatchedPath : PathCall {
     // own setup slot
     int frame(const CamDev* cams, uint32_t slot, uint32_t count, uint32_t f, uint32_t per_launch) const {
         if (slot == 0) {
-            SetupParams sp = setup_params(ctx, cams, W, H, rs);
+            SetupParams sp = setup_params(ctx, ctx->bins, cams, W, H, rs);
             sp.cull = ctx->d_bcull;
             sp.objs = ctx->d_bobjs;
             sp.objs_src = ctx->d_objs;

@@ -52,7 +52,7 @@ int ensure_bins(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
     for (auto& o : ctx->objects)
         if (o.T > kDirectMax) binned_tris += o.T;
     if (!ctx->bin_cap) ctx->bin_cap = std::min(std::max<size_t>(2 * binned_tris, 1u << 16), kMaxBinEntries);
-    const uint32_t phase = row0 % kBinH, tiles_x = (W + 63) / 64;
+    const uint32_t phase = bin_phase(row0), tiles_x = frame_tiles_x(W);
     std::vector<uint64_t> layout{T, nb, W, H, phase, rows, ctx->bin_cap, ctx->scene_gen};
     if (layout == ctx->bins_layout) return ERAY_OK;
     std::vector<uint32_t> kbegin, kobj;
@@ -65,6 +65,12 @@ int ensure_bins(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
     return ERAY_OK;
 }
 }  // namespace
+
+uint32_t binned_before(const eray_ctx* ctx, uint32_t index) {
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < index; ++i) k += ctx->objects[i].T > kDirectMax;
+    return k;
+}
 
 // eray_render_params' band fields as FrameParams encodes them (contiguous: shift 31)
 RowSpan row_span(const eray_render_params* rp) {
@@ -122,7 +128,8 @@ void tag_frames(eray_ctx* ctx, const uint8_t* ppm, uint64_t stride, uint32_t n, 
 
 // Enqueues the per-camera setup of `d_camera` (device) for camera rows [row0, row0 + rows): no
 // host round trip (setup.hip, bins.hip).
-SetupParams setup_params(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint32_t H, const RowSpan& rs) {
+SetupParams setup_params(eray_ctx* ctx, const BinBuffers& bins, const CamDev* d_camera, uint32_t W, uint32_t H,
+                         const RowSpan& rs) {
     SetupParams sp{};
     sp.hot = ctx->d_hot;
     sp.cull = ctx->d_cull;
@@ -152,10 +159,10 @@ SetupParams setup_params(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint
         sp.range = ctx->d_range;
         sp.area = ctx->d_area;
         sp.fkey = ctx->d_fkey;
-        sp.bins_x = ctx->bins.bins_x;
-        sp.phase = ctx->bins.phase;
-        sp.first_local = ctx->bins.first;
-        sp.boff = ctx->bins.boff;
+        sp.bins_x = bins.bins_x;
+        sp.phase = bins.phase;
+        sp.first_local = bins.first;
+        sp.boff = bins.boff;
     }
     return sp;
 }
@@ -165,12 +172,12 @@ SetupParams setup_params(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint
 // keep_all: the general tracer's bins (SetupParams::keep_all)
 int enqueue_setup(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint32_t H, const RowSpan& rs, bool ordered,
                   bool keep_all, int32_t* path_union) {
-    SetupParams sp = setup_params(ctx, d_camera, W, H, rs);
+    SetupParams sp = setup_params(ctx, ctx->bins, d_camera, W, H, rs);
     sp.keep_all = keep_all ? 1u : 0u;
     sp.path_union = path_union;
     sp.union_nobj = sp.nobj;
     HIP_TRY(ctx, launch_camera_setup(sp, ctx->stream));
-    if (sp.binned) HIP_TRY(ctx, launch_bins_build(sp, ctx->bins, (W + 63) / 64, ordered, ctx->stream));
+    if (sp.binned) HIP_TRY(ctx, launch_bins_build(sp, ctx->bins, frame_tiles_x(W), ordered, ctx->stream));
     return ERAY_OK;
 }
 
@@ -218,7 +225,7 @@ int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
         for (uint32_t k = 0; k < K && nobj; ++k)  // (each setup rewrites the rectangles and bin views)
             HIP_TRY(ctx, hipMemcpyAsync(m.objs + (size_t)k * nobj, ctx->d_objs, sizeof(ObjectDesc) * nobj,
                                         hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(ctx, bins_alloc(m.bins, K * T, K * nb, mbegin.data(), mobj.data(), W, H, rs.row0 % kBinH, (W + 63) / 64,
+        HIP_TRY(ctx, bins_alloc(m.bins, K * T, K * nb, mbegin.data(), mobj.data(), W, H, bin_phase(rs.row0), frame_tiles_x(W),
                                 rs.rows, std::min((size_t)K * ctx->bin_cap, kMaxBinEntries), ctx->stream, K));
     }
     ctx->mc_layout = std::move(layout);
@@ -233,7 +240,7 @@ int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
 int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_cams, uint32_t ncam, uint32_t W,
                         uint32_t H, const RowSpan& rs, hipStream_t s, int32_t* path_union) {
     const uint32_t T = ctx->total_tris, nobj = (uint32_t)ctx->objects.size();
-    SetupParams sp = setup_params(ctx, d_cams, W, H, rs);
+    SetupParams sp = setup_params(ctx, m.bins, d_cams, W, H, rs);
     sp.ncam = ncam;
     sp.T1 = T;
     sp.nobj1 = nobj;
@@ -249,14 +256,10 @@ int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_ca
     sp.range = m.range;
     sp.area = m.area;
     sp.fkey = m.fkey;
-    sp.bins_x = m.bins.bins_x;
-    sp.phase = m.bins.phase;
-    sp.first_local = m.bins.first;
-    sp.boff = m.bins.boff;
     sp.path_union = path_union;
     sp.union_nobj = nobj;
     HIP_TRY(ctx, launch_camera_setup(sp, s));
-    HIP_TRY(ctx, launch_bins_build(sp, m.bins, (W + 63) / 64, false, s));
+    HIP_TRY(ctx, launch_bins_build(sp, m.bins, frame_tiles_x(W), false, s));
     return ERAY_OK;
 }
 

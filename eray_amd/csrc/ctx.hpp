@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/eray_hip.h"
+#include "bins.hpp"
 #include "internal.hpp"
 #include "owners.hpp"
 
@@ -123,7 +124,7 @@ struct eray_ctx {
     DeviceBuf<int4> d_range;      // binned faces' bin rectangles, areas, binned-object index
     DeviceBuf<unsigned long long> d_area;
     DeviceBuf<uint32_t> d_fkey;
-    BinBuffers bins;              // (bins.hip's own allocation: bins_alloc / bins_free)
+    BinBuffers bins;              // the scene camera's screen bins (bins.hpp; ensure_bins allocates)
     std::vector<uint64_t> bins_layout;
     uint64_t bins_gen = 0;        // bumped whenever bins_alloc (re)allocates the bin buffers
     size_t bin_cap = 0;           // entry capacity to allocate (grown when a setup overflows)
@@ -176,13 +177,13 @@ struct eray_ctx {
     Event update_join;  // eray_scene_update_object: the other streams' work so far, waited for by `stream`
 
     // Waits for the context's streams, then releases what the members do not own themselves.
+    // Every member that owns device memory enqueued work may still use is released after this
+    // body: the streams are synchronised here first.
     ~eray_ctx() {
         (void)hipSetDevice(device);
         for (hipStream_t s : {stream, (hipStream_t)own_stream, (hipStream_t)mc_stream})
             if (s) (void)hipStreamSynchronize(s);
         gather_plan.reset();  // (while the streams exist)
-        bins_free(bins);
-        for (auto& m : mc) bins_free(m.bins);
     }
 };
 
@@ -242,7 +243,11 @@ FrameSource scene_source(const eray_ctx* ctx, uint32_t W, uint32_t H, const RowS
 void untag_range(eray_ctx* ctx, uintptr_t a, size_t bytes);
 void tag_frames(eray_ctx* ctx, const uint8_t* ppm, uint64_t stride, uint32_t n, const FrameSource& s);
 // Camera setups: one camera's, a path chunk's cameras at once, the scene camera's with its host copy.
-SetupParams setup_params(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint32_t H, const RowSpan& rs);
+// (bins: the buffers the setup's bins are built in, the context's own or a multi-camera set's)
+SetupParams setup_params(eray_ctx* ctx, const BinBuffers& bins, const CamDev* d_camera, uint32_t W, uint32_t H,
+                         const RowSpan& rs);
+// The binned objects before object `index` (its place among the bin keys' objects).
+uint32_t binned_before(const eray_ctx* ctx, uint32_t index);
 int enqueue_setup(eray_ctx* ctx, const CamDev* d_camera, uint32_t W, uint32_t H, const RowSpan& rs, bool ordered,
                   bool keep_all = false, int32_t* path_union = nullptr);
 int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs);

@@ -9,6 +9,7 @@
 
 #include "accel_walk.hpp"
 #include "band_rows.hpp"
+#include "bin_layout.hpp"
 
 namespace eray {
 namespace gpu {
@@ -79,8 +80,7 @@ struct MaterialDesc {
 constexpr uint32_t kCacheTris = 256, kCacheObjects = 16, kCacheLights = 16;
 // Objects with more faces than this are not scanned per wave: screen bins / LDS tiles.
 constexpr uint32_t kDirectMax = 256;
-// Screen bins of large objects' faces: kBinW x kBinH pixels (one wave's 16 x 4 sub-block).
-constexpr uint32_t kBinW = 16, kBinH = 4;
+// (Screen bins of large objects' faces, kBinW x kBinH pixels: bin_layout.hpp.)
 // Bins of 65 to this many entries are sorted by face index (bins.hip bin_sort_kernel); longer
 // ones keep the scatter's order.  In a sorted bin each full 64-entry chunk but the last also
 // carries, in the pad words of its first two entries (low, high half), the union of the pixel
@@ -448,57 +448,6 @@ struct ReachBatch {
 };
 hipError_t launch_reach_light(const ReachBatch& b, const RayAccelView& a, hipStream_t s);
 
-// ------------------------------------------------------------- screen bins (bins.hip)
-// Device arrays of the binned objects' screen bins for one layout (camera size, row phase, the
-// binned objects), all preallocated: a camera's bins are rebuilt on the stream with no host
-// round trip.  Bin key = k * nbins + bin for binned object k; a bin's entries (face relative to
-// the object, pixel mask, intersection record) are unordered — the frame kernel keeps the
-// smallest face index that hits, which is the reference's first hit (object.rs:63-78).
-struct BinBuffers {
-    uint32_t nb = 0, nbins = 0, bins_x = 0, bins_y = 0, phase = 0, T = 0;
-    size_t cap = 0;                       // entry capacity
-    unsigned long long* first = nullptr;  // SetupParams::first_local (T)
-    unsigned long long* boff = nullptr;   // SetupParams::boff (kSetupMaxBlocks + 1)
-    uint32_t nparts = 0, chunk = 0;       // the setup's chunk workgroups and faces per chunk
-    uint32_t* count = nullptr;            // per key (nb * nbins + 1), zero between builds
-    uint32_t* start = nullptr;            // per key + 1
-    uint32_t* kbegin = nullptr;           // tri_begin per binned object
-    uint32_t* kobj = nullptr;             // object index per binned object
-    uint32_t* n = nullptr;                // entries found (device counter, reset by the finaliser)
-    uint32_t* done = nullptr;             // workgroup counter of the finaliser
-    uint32_t* acc = nullptr;              // rectangle accumulators of the non-empty bins (a line per object)
-    uint32_t* part = nullptr;             // 10 per finaliser workgroup: its end objects' partials
-    uint32_t* ekey = nullptr;             // unscattered entries (cap)
-    uint32_t* eface = nullptr;
-    unsigned long long* emask = nullptr;
-    uint32_t* erank = nullptr;            // the entry's place among its bin's entries (count's old value)
-    BinEntry* ent = nullptr;              // bin entries in key order (cap)
-    // detail sub-block list of the rendered rows
-    uint8_t* dflags = nullptr;            // listed sub-blocks whose bin holds more than one chunk
-    uint8_t* dflags_light = nullptr;      // ... and the other listed ones
-    uint32_t* dpacked = nullptr;
-    uint32_t* dlist = nullptr;
-    uint32_t* dlight = nullptr;           // the light ones, appended to dlist after the heavy ones
-    uint32_t* dcount = nullptr;           // [heavy, light] counts
-    uint8_t* docc = nullptr;
-    uint32_t* sortq = nullptr;            // bins to sort by face index (bins.hip bin_sort_kernel)
-    uint32_t* nsort = nullptr;            // their count, zero between builds
-    size_t nsub = 0;
-    void* temp = nullptr;                 // hipcub scratch
-    size_t temp_bytes = 0;
-};
-// (Re)allocates `b` for T triangles, nb binned objects (kbegin / kobj: host arrays), a W x H
-// camera, row phase and `rows` rendered rows, entry capacity `cap` (synchronises `s` when it
-// reallocates); the detail lists of `ncam` cameras (a multi-camera setup, SetupParams::ncam).
-hipError_t bins_alloc(BinBuffers& b, uint32_t T, uint32_t nb, const uint32_t* kbegin, const uint32_t* kobj, uint32_t W,
-                      uint32_t H, uint32_t phase, uint32_t tiles_x, uint32_t rows, size_t cap, hipStream_t s,
-                      uint32_t ncam = 1);
-void bins_free(BinBuffers& b);
-// After launch_camera_setup: the bins of the setup's camera, the binned objects' rectangles
-// narrowed to their non-empty bins and their bin views in the descriptors (or none when the
-// entries overflow the capacity: the frame kernel then scans those objects through LDS tiles),
-// and the detail sub-block list of rows [row0, row0 + rows) with CamState::total_sub.
-hipError_t launch_bins_build(const SetupParams& sp, BinBuffers& b, uint32_t tiles_x, bool ordered, hipStream_t s);
 hipError_t launch_pack_ppm(const float* rgb, uint32_t w, uint32_t h, uint8_t* out, hipStream_t s);
 
 // ----------------------------------------------------------------- frame sources (the gather's)

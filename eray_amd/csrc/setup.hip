@@ -147,7 +147,8 @@ __global__ void __launch_bounds__(kSetupWG) camera_setup_kernel(SetupParams sp, 
                 if (multi && k != ~0u) k += kc * sp.nb1;
                 int4 g = make_int4(1, 0, 1, 0);
                 if (k != ~0u && any) {
-                    // bin row of camera row y: (y + kBinH - phase) / kBinH
+                    // bin column of pixel column x and bin row of camera row y: bin_layout.hpp's bin_col and
+                    // bin_row, (y + kBinH - phase) / kBinH, here on the rectangle's signed bounds
                     g = make_int4(r[0] / (int32_t)kBinW, r[1] / (int32_t)kBinW,
                                   (r[2] + (int32_t)kBinH - (int32_t)sp.phase) / (int32_t)kBinH,
                                   (r[3] + (int32_t)kBinH - (int32_t)sp.phase) / (int32_t)kBinH);

@@ -20,7 +20,9 @@ import pytest
 from eray_amd import capi, dist, meshgen
 from eray_amd.dist import band_camera_rows, band_split
 from eray_amd.frame import MainScene
-from tests.helpers import assert_bit_equal
+from tests.helpers import all_bins as _all_bins
+from tests.helpers import assert_bin_order_and_pads, assert_bit_equal, assert_pair_bins_within_segment_bins
+from tests.helpers import bin_entries as _bin_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -298,15 +300,6 @@ def test_c5_every_64th_row_block_equals_brute_force(gpu, synth1m):
         sc.close()
 
 
-def _bin_entries(gpu, b, cap=1024):
-    tri, mask, pad = (ctypes.c_uint32 * cap)(), (ctypes.c_uint64 * cap)(), (ctypes.c_uint32 * cap)()
-    n = ctypes.c_uint32()
-    assert capi.lib().eray_debug_bin_entries(gpu.handle, 0, b, tri, mask, pad, cap, ctypes.byref(n)) == 0
-    m = min(n.value, cap)
-    return (n.value, np.frombuffer(tri, np.uint32)[:m].copy(), np.frombuffer(mask, np.uint64)[:m].copy(),
-            np.frombuffer(pad, np.uint32)[:m].copy())
-
-
 def test_c5_sorted_bins_carry_later_chunk_masks(gpu, synth1m):
     """C5's bins (1M faces, 7680x4320) as frame_first_hit.hpp first_hit_binned_wave relies on them
     (bins.hip bin_sort_kernel): every bin of 65..1024 entries lists its faces in increasing index —
@@ -334,17 +327,7 @@ def test_c5_sorted_bins_carry_later_chunk_masks(gpu, synth1m):
         for b in pick.tolist():
             n, tri, mask, pad = _bin_entries(gpu, b)
             assert n == counts[b]
-            if n <= 64:
-                assert not pad.any(), f"bin {b}: pads in an unsorted bin"
-                continue
-            assert (np.diff(tri.astype(np.int64)) > 0).all(), f"bin {b} ({n} entries) not in face order"
-            nch = (n + 63) // 64
-            want = np.zeros(n, np.uint32)
-            for c in range(nch - 1):
-                u = np.bitwise_or.reduce(mask[64 * (c + 1):])
-                want[64 * c] = np.uint32(int(u) & 0xFFFFFFFF)
-                want[64 * c + 1] = np.uint32(int(u) >> 32)
-            assert np.array_equal(pad, want), f"bin {b} ({n} entries): later-chunk mask unions"
+            assert_bin_order_and_pads(b, n, tri, mask, pad)
     finally:
         fr.free()
         sc.close()
@@ -480,22 +463,6 @@ def test_culling_margins_on_pixel_corner_rays(gpu, faces):
         sc.close()
 
 
-def _all_bins(gpu):
-    """Every bin of object 0 as built by the last setup: {bin: sorted [(face, mask)]}."""
-    L = capi.lib()
-    st = (ctypes.c_uint64 * 14)()
-    assert L.eray_debug_bin_stats(gpu.handle, 0, st) == 0
-    cap = 4096
-    tri, mask, n = (ctypes.c_uint32 * cap)(), (ctypes.c_uint64 * cap)(), ctypes.c_uint32()
-    out = {}
-    for b in range(int(st[0])):
-        assert L.eray_debug_bin_dump(gpu.handle, 0, b, tri, mask, cap, ctypes.byref(n)) == 0
-        assert n.value <= cap
-        if n.value:
-            out[b] = sorted(zip(tri[: n.value], mask[: n.value]))
-    return out, int(st[13])
-
-
 def test_bin_segments_equal_rectangle_pairs(gpu):
     """The frame setups' pair pass over the faces' bin-rectangle rows (bins.hip
     bin_segments_kernel: per-row pixel ranges from bin_pixels' own double-precision lines) against
@@ -521,16 +488,7 @@ def test_bin_segments_equal_rectangle_pairs(gpu):
             assert ub <= ua, (ub, ua)  # (rows of the rectangles, at most their bins)
             n_pairs = sum(len(v) for v in ba.values())
             assert n_pairs > 10_000
-            extra = 0
-            for b, seg in bb.items():
-                pairs = dict(ba.get(b, []))
-                seg_d = dict(seg)
-                assert len(seg_d) == len(seg), f"bin {b}: a face twice"
-                for f, m in pairs.items():
-                    assert seg_d.get(f) == m, f"bin {b} face {f}: mask {seg_d.get(f)} vs {m} (row0 {row0})"
-                extra += len(seg_d) - len(pairs)
-            assert set(ba) <= set(bb)
-            assert extra <= n_pairs // 20, (extra, n_pairs)
+            assert_pair_bins_within_segment_bins(ba, bb, f"row0 {row0}")
     finally:
         assert L.eray_debug_set_bin_form(gpu.handle, 0) == 0
         sc.close()
