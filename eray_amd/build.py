@@ -109,23 +109,24 @@ DEV_MAIN = os.path.join(TESTS_CPP, "accel_dev_main.cpp")
 REFIT_MAIN = os.path.join(TESTS_CPP, "accel_refit_main.cpp")
 REFIT_ASYNC_MAIN = os.path.join(TESTS_CPP, "accel_refit_async_main.cpp")
 REFIT_HOSTTREE_MAIN = os.path.join(TESTS_CPP, "accel_refit_hosttree_main.cpp")
-# tests/cpp/update_args_main.cpp (headers only)
-UPDATE_ARGS_MAIN = os.path.join(TESTS_CPP, "update_args_main.cpp")
-UPDATE_ARGS_HEADERS = [os.path.join(CSRC, "rays_args.hpp"), os.path.join(ROOT, "include", "eray_hip.h")]
-# tests/cpp/gather_plan_main.cpp (headers only): the multi-GPU gather's planning
-GATHER_PLAN_MAIN = os.path.join(TESTS_CPP, "gather_plan_main.cpp")
-GATHER_PLAN_HEADERS = [os.path.join(CSRC, "gather_plan.hpp"), os.path.join(CSRC, "band_rows.hpp"),
-                       os.path.join(ROOT, "include", "eray_hip.h")]
-# tests/cpp/bin_layout_main.cpp (headers only): the screen bins' sizing
-BIN_LAYOUT_MAIN = os.path.join(TESTS_CPP, "bin_layout_main.cpp")
-BIN_LAYOUT_HEADERS = [os.path.join(CSRC, "bin_layout.hpp"), os.path.join(CSRC, "band_rows.hpp")]
+UPDATE_ARGS_MAIN = os.path.join(TESTS_CPP, "update_args_main.cpp")  # (its test also builds it with the sanitizers)
+# the header-only programs of tests/cpp/ (no library, no GPU): name, the headers each depends on beside its
+# own source, and whether build_host() builds it only where that source is present (a tests/ directory older
+# than the program still gets everything it runs; the program's Python test fails without it)
+_INC = os.path.join(ROOT, "include", "eray_hip.h")
+HEADER_PROGRAMS = [
+    ("update_args_main", ["rays_args.hpp", _INC], False),  # the update's argument checks
+    ("gather_plan_main", ["gather_plan.hpp", "band_rows.hpp", _INC], False),  # the multi-GPU gather's planning
+    ("bin_layout_main", ["bin_layout.hpp", "band_rows.hpp"], True),  # the screen bins' sizing
+    ("frame_plan_main", ["frame_plan.hpp", "frame_params.hpp", "bin_layout.hpp", "band_rows.hpp", _INC], True),  # the frame calls' planning
+]
 
 
 def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> list[str]:
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
     the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
     test_refit_hosttree, accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_hosttree_main, accel_refit_async_main,
-    update_args_main, gather_plan_main, bin_layout_main).  Plain g++: the
+    update_args_main, gather_plan_main, bin_layout_main, frame_plan_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")
@@ -171,7 +172,7 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
         outs.append(exe)
     # the ray-query hierarchy on the CPU (what the programs share is tests/cpp/accel_emul.hpp): the builder and
     # the shared walk; the device-side builder, its refit and the refit on the stream emulated with the headers
-    # their kernels share, and the checker.  No GPU library.  (The update's argument checks follow.)
+    # their kernels share, and the checker.  No GPU library.  (The header-only programs follow.)
     accel_deps = [os.path.join(TESTS_CPP, f) for f in sorted(os.listdir(TESTS_CPP)) if f.endswith(".hpp")]
     accel_deps += [os.path.join(CSRC, h) for h in ACCEL_DEV_HEADERS]
     for name, main_src, more in (("accel_walk_main", WALK_MAIN, [os.path.join(CSRC, "accel_build.cpp")]),
@@ -183,20 +184,12 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
         if force or not _newer(exe, [main_src, *more, *accel_deps]):
             run([cxx, *ACCEL_WALK_FLAGS, main_src, *more, "-o", exe])
         outs.append(exe)
-    exe = os.path.join(BIN_DIR, "update_args_main")
-    if force or not _newer(exe, [UPDATE_ARGS_MAIN, *UPDATE_ARGS_HEADERS]):
-        run([cxx, "-std=c++17", "-O2", "-Wall", UPDATE_ARGS_MAIN, "-o", exe])
-    outs.append(exe)
-    exe = os.path.join(BIN_DIR, "gather_plan_main")
-    if force or not _newer(exe, [GATHER_PLAN_MAIN, *GATHER_PLAN_HEADERS]):
-        run([cxx, "-std=c++17", "-O2", "-Wall", GATHER_PLAN_MAIN, "-o", exe])
-    outs.append(exe)
-    # (only where the program's source is there: a tests/ directory older than bin_layout.hpp still
-    # gets everything it runs; tests/test_bin_layout.py fails without the program)
-    if os.path.exists(BIN_LAYOUT_MAIN):
-        exe = os.path.join(BIN_DIR, "bin_layout_main")
-        if force or not _newer(exe, [BIN_LAYOUT_MAIN, *BIN_LAYOUT_HEADERS]):
-            run([cxx, "-std=c++17", "-O2", "-Wall", BIN_LAYOUT_MAIN, "-o", exe])
+    for name, deps, optional in HEADER_PROGRAMS:
+        main_src, exe = os.path.join(TESTS_CPP, name + ".cpp"), os.path.join(BIN_DIR, name)
+        if optional and not os.path.exists(main_src):
+            continue
+        if force or not _newer(exe, [main_src, *(os.path.join(CSRC, d) for d in deps)]):
+            run([cxx, "-std=c++17", "-O2", "-Wall", main_src, "-o", exe])
         outs.append(exe)
     return outs
 

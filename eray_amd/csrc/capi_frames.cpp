@@ -2,8 +2,11 @@
 // call's FrameParams (prepare_render), eray_render, the cache of captured frame graphs and launch
 // plans, frames in flight into a ring (eray_render_frames*, eray_render_prepare*), the dispatch-timed
 // measurements (eray_time_*) and camera paths with their three setup strategies
-// (eray_render_camera_path*).  The camera setups, bins and frame tags they use are capi_setup.cpp's,
-// the kernels' launchers render.hip's (internal.hpp).  Host code only.
+// (eray_render_camera_path*).  What a call decides before it touches the GPU — the parameter and ring
+// checks, frames per launch, ring slots, the split into graph chunks — is frame_plan.hpp's (no HIP;
+// tests/cpp/frame_plan_main.cpp checks it on the CPU); here are the HIP calls, the context and the
+// strategies.  The camera setups, bins and frame tags they use are capi_setup.cpp's, the kernels'
+// launchers render.hip's (internal.hpp).  Host code only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +32,13 @@ uint32_t trace_accel_objects(const eray_ctx* ctx, uint32_t flags) {
         if (o.T >= ra.min_faces && !(o.lo[0] == o.hi[0] && o.lo[1] == o.hi[1])) return ra.covered;
     return 0u;
 }
+// The most faces of one object (FrameParams::max_object_tris; from the objects: the scene may not be
+// synchronised yet).
+uint32_t max_object_tris(const eray_ctx* ctx) {
+    uint32_t m = 0;
+    for (auto& o : ctx->objects) m = o.T > m ? o.T : m;
+    return m;
+}
 // Frame parameters of a render call.  Culled frames need the camera's setup: when its results
 // are on the host (or `wait`), the detail rectangles / count travel in the kernel arguments
 // (args mode); otherwise the frame kernel reads them from the setup's CamState (device-camera
@@ -41,40 +51,11 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     // anti-aliasing and reflection bounces take the general tracer (trace.hip); bounces only
     // matter when some material has a reflection output (engine.rs:181-182)
     const uint32_t bounces = scene_reflective(ctx) ? rp->bounces : 0u;
-    if (bounces > kMaxBounces)
-        return set_error(ctx, ERAY_E_UNSUPPORTED, "bounces = %u: at most %u reflection levels", rp->bounces,
-                         kMaxBounces);
-    const uint32_t known_flags = ERAY_RENDER_BRUTE_FORCE | ERAY_RENDER_DENSE_DETAIL | ERAY_RENDER_NO_DENSE_DETAIL |
-                                 ERAY_RENDER_SEPARATE_FILL | ERAY_RENDER_NO_SEPARATE_FILL | ERAY_RENDER_SHARED_DETAIL |
-                                 ERAY_RENDER_NO_RAY_ACCEL;
-    if (rp->flags & ~known_flags) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "unknown render flags 0x%x", rp->flags);
     const bool general = rp->anti_aliasing > 0 || bounces > 0;
     uint32_t W, H;
     eray_camera_size(&ctx->camera, &W, &H);
-    if (!rp->band_rows && (uint64_t)rp->row0 + rp->rows > H)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "rows [%u, %u) exceed the camera height %u", rp->row0,
-                         rp->row0 + rp->rows, H);
-    // Image::set indexes y * image.width + x and panics past the end (image.rs:41-43)
-    if (W && H &&
-        (uint64_t)(H - 1) * rp->image_width + (W - 1) >= (uint64_t)rp->image_width * rp->image_height)
-        return set_error(ctx, ERAY_E_OUT_OF_BOUNDS,
-                         "camera size %ux%u does not fit the %ux%u engine image (Image::set panics)", W, H,
-                         rp->image_width, rp->image_height);
-    if (rp->out_ppm && (W != rp->image_width || H != rp->image_height))
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                         "fused PPM output needs camera size == image size; use eray_pack_ppm");
-    if (rp->band_rows) {  // interleaved bands: aligned to the 4-row sub-blocks, inside the camera
-        if (rp->band_rows % 4 || (rp->band_rows & (rp->band_rows - 1)) || rp->band_stride % 4 || rp->row0 % 4 ||
-            rp->band_stride < rp->band_rows)
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                             "bands: band_rows (%u) must be a power of two >= 4, band_stride (%u) and row0 (%u) "
-                             "multiples of 4, band_stride >= band_rows", rp->band_rows, rp->band_stride, rp->row0);
-        const RowSpan rs = row_span(rp);
-        if (rp->rows && (uint64_t)rp->row0 + (uint64_t)((rp->rows - 1) >> rs.band_shift) * rp->band_stride +
-                                ((rp->rows - 1) & rs.band_mask) >= H)
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "bands: %u local rows reach past the camera height %u",
-                             rp->rows, H);
-    }
+    char why[kWhyLen];
+    if (int code = check_render_params(rp, W, H, bounces, why, sizeof why)) return set_error(ctx, code, "%s", why);
     const bool cull = !general && !(rp->flags & ERAY_RENDER_BRUTE_FORCE);
     if (int st = sync_scene(ctx)) return st;
     *empty = !rp->rows || !W;
@@ -107,11 +88,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     p.out_rgb = rp->out_rgb;
     p.out_ppm = rp->out_ppm;
     p.out_face = rp->out_face;
-    // 16-byte row stores: 16-byte aligned rows, and byte offsets of the largest output (f32 RGB)
-    // within 32 bits (the kernels store through buffer resources, hit.hpp stream16)
-    p.aligned = (p.img_w % 16) == 0 && (uint64_t)p.rows * p.img_w * 12u < (1ull << 32) &&
-                ((reinterpret_cast<uintptr_t>(p.out_rgb) | reinterpret_cast<uintptr_t>(p.out_ppm) |
-                  reinterpret_cast<uintptr_t>(p.out_face)) & 15) == 0;
+    p.aligned = rows_aligned(p.img_w, p.rows, p.out_rgb, p.out_ppm, p.out_face);
     p.tris = ctx->d_hot;
     p.shade = ctx->d_shade;
     p.cull = cull ? ctx->d_cull : nullptr;
@@ -119,8 +96,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     p.lights = ctx->d_lights;
     p.nobj = (uint32_t)ctx->objects.size();
     p.nlights = (uint32_t)ctx->lights.size();
-    p.max_object_tris = 0;
-    for (auto& o : ctx->objects) p.max_object_tris = o.T > p.max_object_tris ? o.T : p.max_object_tris;
+    p.max_object_tris = max_object_tris(ctx);
     p.total_tris = ctx->total_tris;
     p.lds_scene = (ctx->total_tris <= kCacheTris && p.nobj <= kCacheObjects && p.nlights <= kCacheLights) ? 1u : 0u;
     p.spec_pow = ctx->spec_pow ? 1u : 0u;
@@ -159,15 +135,8 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
         p.detail_occ = ctx->bins.docc;
     }
     p.launch_flags = rp->flags & ~(ERAY_RENDER_BRUTE_FORCE | ERAY_RENDER_NO_RAY_ACCEL | kLaunchRingBeyondCache);
-    if (!cull) {  // every pixel in detail: one rectangle, the frame (sub-block units)
-        if (p.nobj) {
-            p.nrect = 1;
-            p.rects[0][0] = 0;
-            p.rects[0][1] = (int32_t)((W - 1) / 16);
-            p.rects[0][2] = 0;
-            p.rects[0][3] = (int32_t)((rp->rows - 1) / 4);
-            p.total_sub = (uint32_t)(p.rects[0][1] + 1) * (uint32_t)(p.rects[0][3] + 1);
-        }
+    if (!cull) {  // every pixel in detail
+        whole_frame_rect(W, rp->rows, p.nobj, &p);
         return ERAY_OK;
     }
     if (known) {  // args mode
@@ -217,8 +186,6 @@ int eray_render(eray_ctx* ctx, const eray_render_params* rp) {
 }  // extern "C"
 
 namespace {
-constexpr uint32_t kGraphFrames = 64;
-
 constexpr size_t kGraphCache = 6;
 
 // Appends v's bytes to a graph key.
@@ -273,61 +240,39 @@ std::vector<unsigned char> params_key(const FrameParams& p, uint32_t kind) {
     return key;
 }
 
-// The launch plan of `frames` frames: a graph of `chunk` = min(frames, kGraphFrames) frames,
-// replayed frames / chunk times, and a graph of the remainder (no plain launches, whose host
-// cost can exceed a frame's device time).  chunk = 0: plain launches (null stream, 1 frame).
-// A chunk without a graph (direct_plan) is enqueued frame by frame.
-struct Plan {
-    uint32_t chunk = 0, rest = 0;
+// The launch plan of `frames` frames (frame_plan.hpp PlanShape) with its graphs: a graph per chunk
+// length, replayed; a chunk without a graph (direct_plan) is enqueued frame by frame.
+struct Plan : PlanShape {
     hipGraphExec_t chunk_exec = nullptr, rest_exec = nullptr;
 };
 template <typename Body>
 int ensure_plan(eray_ctx* ctx, const std::vector<unsigned char>& key, uint32_t frames, Body&& body, Plan* plan) {
-    *plan = Plan{};
-    if (!ctx->stream || frames < 2) return ERAY_OK;  // the null stream cannot be captured
-    const uint32_t n = frames < kGraphFrames ? frames : kGraphFrames;
-    if (int st = ensure_graph(ctx, key, n, body, &plan->chunk_exec)) return st;
-    plan->chunk = n;
-    const uint32_t r = frames % n;
-    if (r > 1) {
-        if (int st = ensure_graph(ctx, key, r, body, &plan->rest_exec)) return st;
-        plan->rest = r;
-    }
+    *plan = Plan{graph_plan_shape(frames, ctx->stream != nullptr)};  // the null stream cannot be captured
+    if (plan->chunk)
+        if (int st = ensure_graph(ctx, key, plan->chunk, body, &plan->chunk_exec)) return st;
+    if (plan->rest)
+        if (int st = ensure_graph(ctx, key, plan->rest, body, &plan->rest_exec)) return st;
     return ERAY_OK;
 }
-// The same chunks with no graphs.
-Plan direct_plan(uint32_t frames) {
-    Plan plan;
-    plan.chunk = std::min(frames, kGraphFrames);
-    plan.rest = frames % plan.chunk;
-    return plan;
-}
+Plan direct_plan(uint32_t frames) { return Plan{direct_plan_shape(frames)}; }
 
 // Runs `plan` for `frames` frames of `run`: run.before_chunk(first frame, count) ahead of each
 // chunk, the chunk as its graph's launch or, without one, run.body(first, f, count) per frame
 // f < count; run.plain(f) renders the frames the plan does not cover.
 template <typename Run>
 int replay(eray_ctx* ctx, const Plan& plan, uint32_t frames, const Run& run) {
-    uint32_t done = 0;
-    auto chunk = [&](uint32_t count, hipGraphExec_t exec) -> int {
-        if (int st = run.before_chunk(done, count)) return st;
-        if (exec) {
+    auto chunk = [&](uint32_t first, uint32_t count, bool rest) -> int {
+        if (int st = run.before_chunk(first, count)) return st;
+        if (const hipGraphExec_t exec = rest ? plan.rest_exec : plan.chunk_exec) {
             const hipError_t e = hipGraphLaunch(exec, ctx->stream);
             if (e != hipSuccess) return set_error(ctx, ERAY_E_HIP, "render loop: %s", hipGetErrorString(e));
         } else {
             for (uint32_t f = 0; f < count; ++f)
-                if (int st = run.body(done, f, count)) return st;
+                if (int st = run.body(first, f, count)) return st;
         }
-        done += count;
         return ERAY_OK;
     };
-    while (plan.chunk && done + plan.chunk <= frames)
-        if (int st = chunk(plan.chunk, plan.chunk_exec)) return st;
-    if (plan.rest && done + plan.rest == frames)
-        if (int st = chunk(plan.rest, plan.rest_exec)) return st;
-    for (; done < frames; ++done)
-        if (int st = run.plain(done)) return st;
-    return ERAY_OK;
+    return walk_plan(plan, frames, chunk, [&](uint32_t f) { return run.plain(f); });
 }
 
 // The device time of a stretch of work on a stream, between two events of its own.
@@ -396,82 +341,6 @@ struct LaunchTimers {
         return hipSuccess;
     }
 };
-// Frames in flight (eray_frame_ring): frames of one call are rendered `per_launch` to a kernel
-// launch (FrameParams::nframes), frame k into ring slot k % slots.
-struct Ring {
-    uint32_t slots = 1, per_launch = 1;
-    uint64_t rgb = 0, ppm = 0, face = 0;  // bytes between slots
-};
-// One launch renders at most this many pixels (frames x rows x width) when the library picks the
-// frames per launch, at most kMaxInFlight frames.  Measured (scripts/frames_in_flight.py,
-// profiles/r03/frames_in_flight.jsonl, device us per frame by frames per launch): the cube at
-// 1920x1080 9.3 / 7.6 / 5.4 / 5.0 for 1 / 2 / 4 / 8, at 3840x2160 22.9 / 19.6 for 1 / 2; the 70k
-// stand-in (screen bins, heavier detail work) at 1920x1080 14.2 / 9.2 / 8.2 / 9.2, at 3840x2160
-// 29.1 / 34.5 for 1 / 2.  So two frames of 3840x2160 pixels for small scenes, one for scenes with
-// binned meshes.
-constexpr uint64_t kInFlightPixels = 2ull * 3840ull * 2160ull, kInFlightPixelsBinned = 3840ull * 2160ull;
-constexpr uint32_t kMaxInFlight = 8;
-
-// The library's frames per launch for frames of cam_w x rows pixels and a ring of `slots`.
-uint32_t auto_frames(uint64_t cam_w, uint64_t rows, uint32_t slots, bool binned) {
-    const uint64_t cap = binned ? kInFlightPixelsBinned : kInFlightPixels;
-    uint32_t F = 1;
-    while (F * 2 <= kMaxInFlight && F * 2 <= slots && (uint64_t)(F * 2) * cam_w * rows <= cap) F *= 2;
-    return F;
-}
-
-int make_ring(eray_ctx* ctx, const eray_render_params* rp, const FrameParams& p, const eray_frame_ring* r, Ring* out) {
-    *out = Ring{};
-    if (!r) return ERAY_OK;
-    if (!r->slots || r->slots > 64 || (r->slots & (r->slots - 1)))
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "ring: slots (%u) must be a power of two <= 64", r->slots);
-    const uint64_t px = (uint64_t)rp->rows * rp->image_width;
-    const uint64_t need[3] = {px * 12u, px * 3u, px * 4u};
-    const uint64_t stride[3] = {r->rgb_stride, r->ppm_stride, r->face_stride};
-    const void* ptr[3] = {rp->out_rgb, rp->out_ppm, rp->out_face};
-    for (int k = 0; k < 3; ++k) {
-        if (!ptr[k] || r->slots == 1) continue;
-        if (stride[k] % 16 || stride[k] < need[k])
-            return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
-                             "ring: output %d's slot stride %llu must be a multiple of 16 of at least %llu bytes", k,
-                             (unsigned long long)stride[k], (unsigned long long)need[k]);
-    }
-    if (r->frames_per_launch && (r->frames_per_launch > r->slots || (r->frames_per_launch & (r->frames_per_launch - 1))))
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "ring: frames_per_launch (%u) must be a power of two <= slots (%u)",
-                         r->frames_per_launch, r->slots);
-    out->slots = r->slots;
-    out->rgb = r->slots > 1 ? r->rgb_stride : 0;
-    out->ppm = r->slots > 1 ? r->ppm_stride : 0;
-    out->face = r->slots > 1 ? r->face_stride : 0;
-    uint32_t F = 1;
-    if (p.aa || p.bounces || r->slots == 1) {
-        F = 1;  // the general tracer renders one frame per launch
-    } else if (r->frames_per_launch) {
-        F = r->frames_per_launch;
-    } else {
-        F = auto_frames(p.cam_w, p.rows, r->slots, p.max_object_tris > kDirectMax);
-    }
-    out->per_launch = F;
-    return ERAY_OK;
-}
-
-// The launch parameters of frames [f, f + count) of a call: ring slot f % slots onwards (slots is
-// a multiple of per_launch, so a launch's frames never wrap).
-FrameParams ring_frames(const FrameParams& p, const Ring& r, uint32_t f, uint32_t count) {
-    FrameParams q = p;
-    const uint64_t slot = f % r.slots;
-    q.nframes = count;
-    q.rgb_stride = r.rgb;
-    q.ppm_stride = r.ppm;
-    q.face_stride = r.face;
-    if (q.out_rgb) q.out_rgb = reinterpret_cast<float*>(reinterpret_cast<char*>(q.out_rgb) + slot * r.rgb);
-    if (q.out_ppm) q.out_ppm += slot * r.ppm;
-    if (q.out_face) q.out_face = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(q.out_face) + slot * r.face);
-    const uint64_t ring_bytes = (uint64_t)r.slots * ((q.out_rgb ? r.rgb : 0) + (q.out_ppm ? r.ppm : 0) + (q.out_face ? r.face : 0));
-    if (ring_bytes > kInfinityCacheBytes) q.launch_flags |= kLaunchRingBeyondCache;
-    return q;
-}
-
 std::vector<unsigned char> ring_key(std::vector<unsigned char> key, const Ring& r) {
     append(key, r);
     return key;
@@ -502,8 +371,7 @@ struct StaticRing {
     }
     int before_chunk(uint32_t, uint32_t) const { return ERAY_OK; }
     int body(uint32_t, uint32_t f, uint32_t n) const {
-        if (f % r.per_launch) return ERAY_OK;
-        HIP_TRY(ctx, launch_frame(ctx, ring_frames(p, r, f, std::min(r.per_launch, n - f))));
+        if (const uint32_t nf = launch_frames(f, n, r.per_launch)) HIP_TRY(ctx, launch_frame(ctx, ring_frames(p, r, f, nf)));
         return ERAY_OK;
     }
     int plain(uint32_t f) const { return body(0, f, frames); }
@@ -552,7 +420,112 @@ struct RingCall {
     RingCall(eray_ctx* ctx, const eray_render_params* rp, const eray_frame_ring* ring, bool any, SetupWait wait) {
         bool empty = false;
         if ((st = prepare_render(ctx, rp, &p, &empty, wait)) || empty || !any) return;
-        go = !(st = make_ring(ctx, rp, p, ring, &r));
+        char why[kWhyLen];
+        if (int code = make_ring(rp, p, ring, &r, why, sizeof why)) st = set_error(ctx, code, "%s", why);
+        go = !st;
+    }
+};
+
+// A dispatch-timed call: max(1, frames / per_launch) full launches of the call's ring frames as plain
+// launches, each with start / end events of its own, then the wait, the frame kernel's times and the
+// slots' tags.  The measurement `m` says what differs: kWhat (its messages' prefix), kEvents per
+// launch, args() — the check of its own arguments, ahead of the call's — accepts(p), enqueue(q, t, l)
+// — launch l, with frame parameters q — and finish(p, rp, t, res, src): the result's other fields and
+// the source the slots hold now.
+template <typename M>
+int time_launches(eray_ctx* ctx, const eray_render_params* rp, const eray_frame_ring* ring, uint32_t frames,
+                  eray_kernel_times* out, M m) {
+    if (!out) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "%s: out is null", M::kWhat);
+    *out = eray_kernel_times{};
+    if (int st = m.args(ctx)) return st;
+    const RingCall c(ctx, rp, ring, frames != 0, SetupWait::kYes);
+    if (!c.go) return c.st;
+    if (int st = m.accepts(ctx, c.p)) return st;
+    const uint32_t F = c.r.per_launch, L = std::max(1u, frames / F);
+    LaunchTimers t(L, M::kEvents);
+    HIP_TRY(ctx, t.create());
+    for (uint32_t l = 0; l < L; ++l) HIP_TRY(ctx, m.enqueue(ctx, ring_frames(c.p, c.r, l * F, F), t, l));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    eray_kernel_times res{};
+    HIP_TRY(ctx, t.reduce(F, &res));
+    FrameSource src;
+    if (int st = m.finish(ctx, c.p, rp, t, &res, &src)) return st;
+    tag_frames(ctx, c.p.out_ppm, c.r.ppm, std::min(L * F, c.r.slots), src);
+    *out = res;
+    return ERAY_OK;
+}
+
+// eray_time_frames_ring: the frame kernel, and the separate fill where the launch shape has one.
+struct FrameTiming {
+    static constexpr const char* kWhat = "kernel timing";
+    static constexpr uint32_t kEvents = 4;  // per launch: the frame kernel's pair, the separate fill's pair
+    std::vector<uint32_t> fill_used;
+    int args(eray_ctx*) const { return ERAY_OK; }
+    int accepts(eray_ctx* ctx, const FrameParams& p) const {
+        if (p.aa || p.bounces)
+            return set_error(ctx, ERAY_E_UNSUPPORTED, "kernel timing: the frame kernel only (no anti-aliasing or bounces)");
+        return ERAY_OK;
+    }
+    hipError_t enqueue(eray_ctx* ctx, const FrameParams& q, const LaunchTimers& t, uint32_t l) {
+        if (fill_used.empty()) fill_used.assign(t.launches, 0u);
+        LaunchCtx lc = ctx->lc;
+        lc.frame_t[0] = t.at(l, 0);
+        lc.frame_t[1] = t.at(l, 1);
+        lc.fill_t[0] = t.at(l, 2);
+        lc.fill_t[1] = t.at(l, 3);
+        lc.fill_used = &fill_used[l];
+        return launch_render(q, lc, ctx->stream);
+    }
+    int finish(eray_ctx* ctx, const FrameParams& p, const eray_render_params* rp, const LaunchTimers& t,
+               eray_kernel_times* res, FrameSource* src) const {
+        double fill = 0.0, span = 0.0;
+        uint32_t nfill = 0;
+        for (uint32_t l = 0; l < t.launches; ++l) {
+            float s = 0.0f;
+            HIP_TRY(ctx, hipEventElapsedTime(&s, t.at(l, 0), t.at(l, 1)));
+            if (fill_used[l]) {  // the separate fill beside it: both kernels' span, from the frame kernel's start
+                float f0 = 0.0f, f1 = 0.0f, fk = 0.0f;
+                HIP_TRY(ctx, hipEventElapsedTime(&fk, t.at(l, 2), t.at(l, 3)));
+                HIP_TRY(ctx, hipEventElapsedTime(&f0, t.at(l, 0), t.at(l, 2)));
+                HIP_TRY(ctx, hipEventElapsedTime(&f1, t.at(l, 0), t.at(l, 3)));
+                fill += fk;
+                ++nfill;
+                s = std::max(s, f1) - std::min(0.0f, f0);
+            }
+            span += s;
+        }
+        res->fill_kernel_ms = nfill ? (float)(fill / nfill) : 0.0f;
+        res->launch_span_ms = (float)(span / t.launches);
+        *src = render_source(ctx, p, rp);
+        return ERAY_OK;
+    }
+};
+
+// eray_time_write_ceiling: the frames' background bytes as a plain write stream.
+struct CeilingTiming {
+    static constexpr const char* kWhat = "write ceiling";
+    static constexpr uint32_t kEvents = 2;
+    uint32_t wgs_per_cu;
+    int args(eray_ctx* ctx) const {
+        if (wgs_per_cu < 1 || wgs_per_cu > 8)
+            return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "write ceiling: %u workgroups per CU (1..8)", wgs_per_cu);
+        return ERAY_OK;
+    }
+    int accepts(eray_ctx* ctx, const FrameParams& p) const {
+        if (!p.aligned || p.img_w % 64u || p.rows % 4u)
+            return set_error(ctx, ERAY_E_UNSUPPORTED, "write ceiling: whole 64x4 blocks only (%ux%u, aligned %u)", p.img_w,
+                             p.rows, p.aligned);
+        return ERAY_OK;
+    }
+    hipError_t enqueue(eray_ctx* ctx, const FrameParams& q, const LaunchTimers& t, uint32_t l) const {
+        const hipEvent_t pair[2] = {t.at(l, 0), t.at(l, 1)};
+        return launch_write_ceiling(q, wgs_per_cu, pair, ctx->stream);
+    }
+    int finish(eray_ctx*, const FrameParams&, const eray_render_params*, const LaunchTimers&, eray_kernel_times* res,
+               FrameSource* src) const {
+        res->launch_span_ms = res->frame_kernel_ms;
+        *src = FrameSource{kSrcOther};  // the slots now hold background frames, not renders of the scene
+        return ERAY_OK;
     }
 };
 }  // namespace
@@ -568,12 +541,10 @@ int eray_render_prepare_ring(eray_ctx* ctx, const eray_render_params* rp, const 
 
 uint32_t eray_frames_per_launch(eray_ctx* ctx, const eray_render_params* rp, uint32_t slots) {
     if (!ctx || !rp || !slots) return 1u;
-    if (rp->anti_aliasing || rp->bounces) return 1u;
     uint32_t W, H;
     eray_camera_size(&ctx->camera, &W, &H);
-    bool binned = false;  // (from the objects: the scene may not be synchronised yet, ctx->binned)
-    for (auto& o : ctx->objects) binned |= o.T > kDirectMax;
-    return auto_frames(W, rp->rows, slots, binned);
+    // (bounces as given: whether a material reflects is not asked here)
+    return frames_per_launch(rp->anti_aliasing || rp->bounces, slots, 0, W, rp->rows, max_object_tris(ctx));
 }
 
 int eray_render_prepare(eray_ctx* ctx, const eray_render_params* rp, uint32_t frames) {
@@ -599,81 +570,12 @@ int eray_render_frames(eray_ctx* ctx, const eray_render_params* rp, uint32_t fra
 
 int eray_time_frames_ring(eray_ctx* ctx, const eray_render_params* rp, const eray_frame_ring* ring, uint32_t frames,
                           eray_kernel_times* out) {
-    if (!out) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "kernel timing: out is null");
-    *out = eray_kernel_times{};
-    const RingCall c(ctx, rp, ring, frames != 0, SetupWait::kYes);
-    if (!c.go) return c.st;
-    const FrameParams& p = c.p;
-    const Ring& r = c.r;
-    if (p.aa || p.bounces)
-        return set_error(ctx, ERAY_E_UNSUPPORTED, "kernel timing: the frame kernel only (no anti-aliasing or bounces)");
-    const uint32_t F = r.per_launch, L = std::max(1u, frames / F);
-    LaunchTimers t(L, 4);  // per launch: the frame kernel's pair, the separate fill's pair
-    HIP_TRY(ctx, t.create());
-    std::vector<uint32_t> fill_used(L, 0u);
-    for (uint32_t l = 0; l < L; ++l) {
-        LaunchCtx lc = ctx->lc;
-        lc.frame_t[0] = t.at(l, 0);
-        lc.frame_t[1] = t.at(l, 1);
-        lc.fill_t[0] = t.at(l, 2);
-        lc.fill_t[1] = t.at(l, 3);
-        lc.fill_used = &fill_used[l];
-        HIP_TRY(ctx, launch_render(ring_frames(p, r, l * F, F), lc, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    eray_kernel_times res{};
-    HIP_TRY(ctx, t.reduce(F, &res));
-    double fill = 0.0, span = 0.0;
-    uint32_t nfill = 0;
-    for (uint32_t l = 0; l < L; ++l) {
-        float s = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&s, t.at(l, 0), t.at(l, 1)));
-        if (fill_used[l]) {  // the separate fill beside it: both kernels' span, from the frame kernel's start
-            float f0 = 0.0f, f1 = 0.0f, fk = 0.0f;
-            HIP_TRY(ctx, hipEventElapsedTime(&fk, t.at(l, 2), t.at(l, 3)));
-            HIP_TRY(ctx, hipEventElapsedTime(&f0, t.at(l, 0), t.at(l, 2)));
-            HIP_TRY(ctx, hipEventElapsedTime(&f1, t.at(l, 0), t.at(l, 3)));
-            fill += fk;
-            ++nfill;
-            s = std::max(s, f1) - std::min(0.0f, f0);
-        }
-        span += s;
-    }
-    tag_frames(ctx, p.out_ppm, r.ppm, std::min(L * F, r.slots), render_source(ctx, p, rp));
-    res.fill_kernel_ms = nfill ? (float)(fill / nfill) : 0.0f;
-    res.launch_span_ms = (float)(span / L);
-    *out = res;
-    return ERAY_OK;
+    return time_launches(ctx, rp, ring, frames, out, FrameTiming{});
 }
 
 int eray_time_write_ceiling(eray_ctx* ctx, const eray_render_params* rp, const eray_frame_ring* ring, uint32_t frames,
                             uint32_t wgs_per_cu, eray_kernel_times* out) {
-    if (!out) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "write ceiling: out is null");
-    *out = eray_kernel_times{};
-    if (wgs_per_cu < 1 || wgs_per_cu > 8)
-        return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "write ceiling: %u workgroups per CU (1..8)", wgs_per_cu);
-    const RingCall c(ctx, rp, ring, frames != 0, SetupWait::kYes);
-    if (!c.go) return c.st;
-    const FrameParams& p = c.p;
-    const Ring& r = c.r;
-    if (!p.aligned || p.img_w % 64u || p.rows % 4u)
-        return set_error(ctx, ERAY_E_UNSUPPORTED, "write ceiling: whole 64x4 blocks only (%ux%u, aligned %u)", p.img_w,
-                         p.rows, p.aligned);
-    const uint32_t F = r.per_launch, L = std::max(1u, frames / F);
-    LaunchTimers t(L, 2);
-    HIP_TRY(ctx, t.create());
-    for (uint32_t l = 0; l < L; ++l) {
-        const hipEvent_t pair[2] = {t.at(l, 0), t.at(l, 1)};
-        HIP_TRY(ctx, launch_write_ceiling(ring_frames(p, r, l * F, F), wgs_per_cu, pair, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    eray_kernel_times res{};
-    HIP_TRY(ctx, t.reduce(F, &res));
-    // the slots now hold background frames, not renders of the scene
-    tag_frames(ctx, p.out_ppm, r.ppm, std::min(L * F, r.slots), FrameSource{kSrcOther});
-    res.launch_span_ms = res.frame_kernel_ms;
-    *out = res;
-    return ERAY_OK;
+    return time_launches(ctx, rp, ring, frames, out, CeilingTiming{wgs_per_cu});
 }
 
 }  // extern "C"
@@ -795,8 +697,9 @@ struct BatchedPath : PathCall {
             sp.union_nobj = nobj;
             HIP_TRY(ctx, launch_camera_setup_batch(sp, count, ctx->stream));
         }
-        if (slot % per_launch) return ERAY_OK;
-        FrameParams q = ring_frames(p, r, f, std::min(per_launch, count - slot));
+        const uint32_t nf = launch_frames(slot, count, per_launch);
+        if (!nf) return ERAY_OK;
+        FrameParams q = ring_frames(p, r, f, nf);
         q.cam_state = ctx->d_bstate + slot;
         q.cull = ctx->d_bcull + (size_t)slot * T;
         q.objects = ctx->d_bobjs + (size_t)slot * nobj;
@@ -819,7 +722,7 @@ struct MultiPath : PathCall {
     using PathCall::PathCall;
     int prepare(Plan* plan) {
         if (int st = ensure_multi(ctx, W, H, rs)) return st;
-        while (ctx->mc_k % r.per_launch) r.per_launch /= 2;  // frames in flight within one build: per_launch divides mc_k
+        r.per_launch = fit_per_launch(r.per_launch, ctx->mc_k);  // frames in flight within one build: per_launch divides mc_k
         *plan = direct_plan(n);
         return ERAY_OK;
     }
@@ -849,8 +752,8 @@ struct MultiPath : PathCall {
                 HIP_TRY(ctx, hipEventRecord(ctx->mc_ready[(b + 1) & 1u], ctx->mc_stream));
             }
         }
-        if (slot % r.per_launch) return ERAY_OK;  // rendered by the launch of slot - slot % per_launch
-        const uint32_t nsub = (uint32_t)m.bins.nsub, nf = std::min(r.per_launch, count - slot);
+        const uint32_t nsub = (uint32_t)m.bins.nsub, nf = launch_frames(slot, count, r.per_launch);
+        if (!nf) return ERAY_OK;  // rendered by the launch of slot - slot % per_launch
         FrameParams q = ring_frames(p, r, f, nf);
         q.cam_state = m.state + k;
         q.cull = m.cull + (size_t)k * T;

@@ -72,14 +72,6 @@ uint32_t binned_before(const eray_ctx* ctx, uint32_t index) {
     return k;
 }
 
-// eray_render_params' band fields as FrameParams encodes them (contiguous: shift 31)
-RowSpan row_span(const eray_render_params* rp) {
-    if (!rp->band_rows) return RowSpan{rp->row0, rp->rows, 31u, 0x7fffffffu, 0u};
-    uint32_t shift = 0;
-    while ((1u << shift) < rp->band_rows) ++shift;
-    return RowSpan{rp->row0, rp->rows, shift, rp->band_rows - 1u, rp->band_stride};
-}
-
 FrameSource frame_source(uint32_t kind, uint64_t key, uint32_t W, uint32_t H, const RowSpan& rs) {
     FrameSource s;
     s.kind = kind;

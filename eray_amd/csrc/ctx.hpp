@@ -17,6 +17,7 @@
 
 #include "../../include/eray_hip.h"
 #include "bins.hpp"
+#include "frame_plan.hpp"
 #include "internal.hpp"
 #include "owners.hpp"
 
@@ -231,12 +232,7 @@ inline int use_device(eray_ctx* ctx) {
 int sync_scene(eray_ctx* ctx);
 
 // ---- the frame path's per-camera state (capi_setup.cpp) ----
-// The rendered rows of a call: camera rows [row0, row0 + rows), or rows local rows of
-// interleaved bands (eray_render_params::band_rows).
-struct RowSpan {
-    uint32_t row0, rows, band_shift, band_mask, band_stride;
-};
-RowSpan row_span(const eray_render_params* rp);
+// (RowSpan, the rendered rows of a call, and row_span: frame_plan.hpp.)
 // Source tags of rendered frames, and which PPM slots hold which (eray_gather_frames).
 FrameSource frame_source(uint32_t kind, uint64_t key, uint32_t W, uint32_t H, const RowSpan& rs);
 FrameSource scene_source(const eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs);

@@ -10,6 +10,7 @@
 #include "accel_walk.hpp"
 #include "band_rows.hpp"
 #include "bin_layout.hpp"
+#include "frame_params.hpp"
 
 namespace eray {
 namespace gpu {
@@ -78,8 +79,7 @@ struct MaterialDesc {
 
 // Scenes up to these sizes are preloaded whole into each frame workgroup's LDS.
 constexpr uint32_t kCacheTris = 256, kCacheObjects = 16, kCacheLights = 16;
-// Objects with more faces than this are not scanned per wave: screen bins / LDS tiles.
-constexpr uint32_t kDirectMax = 256;
+// (kDirectMax, the largest object scanned per wave: frame_params.hpp.)
 // (Screen bins of large objects' faces, kBinW x kBinH pixels: bin_layout.hpp.)
 // Bins of 65 to this many entries are sorted by face index (bins.hip bin_sort_kernel); longer
 // ones keep the scatter's order.  In a sorted bin each full 64-entry chunk but the last also
@@ -87,12 +87,6 @@ constexpr uint32_t kDirectMax = 256;
 // masks of every later chunk: the frame kernel stops the bin once no pixel that can still improve
 // is covered by what is left (frame_first_hit.hpp first_hit_binned_wave).
 constexpr uint32_t kBinSortMax = 1024;
-// Detail rectangles carried in the kernel arguments (more objects: merged into the last one).
-constexpr int kMaxRects = 8;
-// Deepest reflection recursion the general tracer keeps frames for (Engine::bounces).
-constexpr uint32_t kMaxBounces = 16;
-// Frames one launch may render (eray_frame_ring::frames_per_launch <= slots <= 64).
-constexpr uint32_t kMaxFramesPerLaunch = 64;
 // The frame kernel reads triangle records (TriHot 48 B, TriShade 64 B) and bin entries (64 B) by
 // buffer loads with 32-bit byte offsets (frame_scene.hpp load_rec): a scene holds fewer than 2^26
 // triangles (eray_scene_add_object refuses more) and a bin buffer at most 2^26 entries (a setup
@@ -104,8 +98,6 @@ constexpr size_t kMaxBinEntries = (size_t)1 << 26;
 // plan's rank table) lives in a scratch block allocated with the context — so no rank can fail to
 // enter a collective its peers have entered for want of memory.
 constexpr size_t kCollScratchBytes = 32u << 10;
-// The MI355X Infinity Cache (the die's last-level cache, MI355X_MICROARCH.md).
-constexpr uint64_t kInfinityCacheBytes = 256ull << 20;
 
 // One entry of a screen bin (bins.hip): a face that may be hit in the bin, its intersection
 // record, the bin's pixels it may cover (bit row * kBinW + column) and its index relative to the
@@ -166,100 +158,11 @@ struct alignas(16) CamState {
     int32_t rects[kMaxRects][4];  // x0, x1, y0, y1 (inclusive)
 };
 
-constexpr uint32_t kTraceSkipTris = 256;  // general tracer: largest scene with the background skip
 // general tracer: a binned sub-block whose bin holds more entries is searched by a whole
 // workgroup (trace.hip; the tracer's setup lists those first, bins.hip detail_flags_kernel)
 constexpr uint32_t kTraceHeavyMin = 192;
 
-struct FrameParams {
-    // camera (camera.rs:57-76)
-    float cx, cy, cz;
-    float ratio;  // fov0 / fov1
-    float z_dist;
-    uint32_t cam_w, cam_h;
-    // output
-    uint32_t img_w, img_h;
-    uint32_t row0, rows;
-    // interleaved row bands (multi-GPU balance): local row j is camera row
-    // row0 + (j >> band_shift) * band_stride + (j & band_mask) (band_rows = 1 << band_shift, a
-    // power of two); a contiguous block is band_shift = 31, band_mask = 0x7fffffff (row0 + j)
-    uint32_t band_shift, band_mask, band_stride;
-    float* out_rgb;
-    uint8_t* out_ppm;
-    int32_t* out_face;
-    uint32_t aligned;  // img_w % 16 == 0 and 16-byte aligned outputs: 16-byte row stores
-    // scene
-    const TriHot* tris;
-    const TriShade* shade;
-    const TriCull* cull;  // nullptr: brute force
-    const ObjectDesc* objects;
-    const LightDesc* lights;
-    uint32_t nobj, nlights;
-    uint32_t max_object_tris;  // selects the kernel variant with LDS triangle tiles
-    uint32_t total_tris;
-    uint32_t lds_scene;        // the scene is small enough to preload into LDS (kCache*)
-    uint32_t nrect;            // detail rectangles (sub-block units: 16 px x 4 rank-local rows,
-    uint32_t total_sub;        // inclusive) and the number of sub-blocks they cover, counting
-    int32_t rects[kMaxRects][4];  // overlaps once: x0, x1, y0, y1
-    uint32_t spec_pow;         // some material has a specular-power output (powf != identity)
-    uint32_t example_mat;      // some material evaluates main.rs's graph per hit (example)
-    uint32_t tiles_x;    // 64 x 4 pixel blocks per row
-    uint32_t bins_x;     // screen bins per row
-    uint32_t bin_phase;  // bins start at camera rows bin_phase + k * kBinH (row0 % kBinH)
-    // Detail sub-block list (scenes with binned objects, bins.hip detail_list_kernel): the j-th
-    // detail sub-block is detail_list[j] = sy << 16 | sx (sub-block units, rank-local rows) and
-    // bit i of detail_occ[block] marks sub-block i of 64 x 4 block `block` as listed.  Null: the
-    // detail rectangles enumerate the sub-blocks.
-    const uint32_t* detail_list;
-    const uint8_t* detail_occ;
-    // the ordered detail list's heavy sub-blocks (its first detail_heavy[0] entries: a bin of more
-    // than one 64-entry chunk), or null (an unordered list: every sub-block treated as heavy)
-    const uint32_t* detail_heavy;
-    uint32_t detail_wgs;  // most workgroups of the frame kernel's grid doing detail work (0: all)
-    uint32_t fill_first;  // the fill workgroups take the grid's first block indices (dispatched first)
-    uint32_t separate_fill;  // the frame kernel does detail work only; fill_kernel writes the background
-    uint32_t fill_cap;       // at most this many workgroups write the background (0: no cap)
-    // device-camera mode: camera, detail rectangles and detail count come from the setup
-    // kernels' CamState (the host has not read them back); null: the fields above hold them
-    const CamState* cam_state;
-    // device-camera mode's fill reservation (launch_frame_kernel computes it on the host in
-    // args mode): detail workgroups at the default share and at the small-scene share used
-    // when the detail sub-blocks exceed one round (frame_kernel decides from the count)
-    uint32_t detail_wgs_alt;
-    uint32_t launch_flags;  // ERAY_RENDER_* launch overrides (dense / separate fill), part of the plan key
-    // general tracer (trace.hip): anti-aliasing rays per pixel, reflection depth, jitter seed;
-    // aa == 0 && bounces == 0 selects the frame kernel
-    uint32_t aa, bounces;
-    uint32_t seed_lo, seed_hi;
-    // trace_kernel's culling records for this camera (scenes of at most kTraceSkipTris faces;
-    // null: no background skip), written by trace_cull_kernel when the camera or the scene changes
-    TriCull* trace_cull;
-    // trace_kernel's camera rays scan the binned objects' screen bins (a setup with
-    // SetupParams::keep_all; the descriptors' bin views and rectangles), else every face
-    uint32_t trace_bins;
-    // ... over the setup's detail list (the sub-blocks some ray of which may hit a face; detail_occ
-    // per 64 x 4 block): trace_heavy_kernel's workgroups take the heavy head of the list, a
-    // workgroup per sub-block; trace_binned_kernel's first trace_fill_wgs workgroups write the
-    // background of the unlisted sub-blocks and the next trace_light_wgs the light list, a wave
-    // per sub-block
-    uint32_t trace_heavy_wgs, trace_fill_wgs, trace_light_wgs;
-    // Frames in flight: one launch renders `nframes` (>= 1) independent frames, its workgroups
-    // dealt round-robin over them (frame_kernel).  Frame f writes out_* + f * *_stride (bytes,
-    // multiples of 16) and, with dev_slots, reads the batched per-camera setup of slot f
-    // (cam_state + f, cull + f * total_tris, objects + f * nobj: launch_camera_setup_batch) and,
-    // for scenes with binned objects (the multi-camera setup), its detail list at detail_list +
-    // f * dlist_stride and occupancy at detail_occ + f * dlist_stride / 4.
-    uint32_t nframes;
-    uint32_t dev_slots;
-    uint32_t dlist_stride;
-    // device-camera mode with a split detail list of this capacity (0: none): list position j of
-    // CamState::heavy_sub heavy sub-blocks is j, of a light one dlist_split - 1 - (j - heavy_sub)
-    uint32_t dlist_split;
-    uint64_t rgb_stride, ppm_stride, face_stride;
-    // frame stores also non-temporal (launch_render: a launch whose outputs exceed the 256 MiB
-    // Infinity Cache — the frame's lines then do not evict what the detail waves read back)
-    uint32_t store_nt;
-};
+// (FrameParams, the frame launch's argument record: frame_params.hpp.)
 
 // Byte offsets of the LDS scene copy: [ObjectDesc x nobj | LightDesc x nl | TriCull x n (if
 // culling) | TriHot x n | TriShade x n]; every section is a whole number of 16-B words.
@@ -378,11 +281,6 @@ __device__ __forceinline__ void union_rect(int32_t* u, uint32_t nobj, uint32_t o
 }
 // Writes `cam` into the device camera slot (kernel arguments: no host staging buffer to race).
 hipError_t launch_set_camera(const CamDev& cam, CamDev* slot, hipStream_t s);
-// Launch overrides of eray_render_params::flags (eray_hip.h ERAY_RENDER_*) the frame launcher reads.
-constexpr uint32_t kLaunchDense = 2u, kLaunchNoDense = 4u, kLaunchSeparateFill = 8u, kLaunchNoSeparateFill = 16u,
-                   kLaunchSharedDetail = 32u;
-// (internal, set per launch by the ring plan: the ring's slots together exceed the Infinity Cache)
-constexpr uint32_t kLaunchRingBeyondCache = 1u << 16;
 // The ray-query hierarchy of the scene (accel_walk.hpp; built by eray_scene_build_ray_accel): per
 // object a record (has == 0: the object keeps the LDS tiles), the nodes, and the leaf-ordered byte
 // copies of the face records with their original indices.  objs null: no hierarchy.
