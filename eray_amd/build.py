@@ -24,8 +24,8 @@ OBJ = os.path.join(PKG, "_obj")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "liberay_hip.so")
 
-SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "capi_setup.cpp",
-           "capi_frames.cpp", "capi_rays.cpp", "comm.cpp", "gather_debug.cpp", "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
+SOURCES = ["render.hip", "setup.hip", "trace.hip", "rays.hip", "bins.hip", "shaderlib.hip", "capi.cpp", "capi_scene.cpp",
+           "capi_debug.cpp", "capi_setup.cpp", "capi_frames.cpp", "capi_rays.cpp", "comm.cpp", "gather_debug.cpp", "objload.cpp", "accel_build.cpp", "accel_check.cpp", "accel_dev.hip"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
             f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include"),
@@ -119,6 +119,8 @@ HEADER_PROGRAMS = [
     ("gather_plan_main", ["gather_plan.hpp", "band_rows.hpp", _INC], False),  # the multi-GPU gather's planning
     ("bin_layout_main", ["bin_layout.hpp", "band_rows.hpp"], True),  # the screen bins' sizing
     ("frame_plan_main", ["frame_plan.hpp", "frame_params.hpp", "bin_layout.hpp", "band_rows.hpp", _INC], True),  # the frame calls' planning
+    ("scene_build_main", ["scene_build.hpp", "texel_prog.hpp", "device_math.hpp", "glibc_cosf.hpp", "glibc_powf.hpp",
+                          "frame_params.hpp", _INC], True),  # the scene upload's descriptors and texel programs
 ]
 
 
@@ -126,7 +128,7 @@ def build_host(jobs: int = 4, verbose: bool = False, force: bool = False) -> lis
     """The C++ host (include/eray/, eray_amd/host/): liberay_host.so over the C-ABI library,
     the eray_main CLI (main.rs) and the tests/cpp/ test binaries (test_host, test_rays, test_accel, test_accel_dev, test_reach, test_update,
     test_refit_hosttree, accel_walk_main, accel_dev_main, accel_refit_main, accel_refit_hosttree_main, accel_refit_async_main,
-    update_args_main, gather_plan_main, bin_layout_main, frame_plan_main).  Plain g++: the
+    update_args_main, gather_plan_main, bin_layout_main, frame_plan_main, scene_build_main).  Plain g++: the
     host code never includes HIP headers."""
     hip_lib = build(jobs, verbose, force)
     host = os.path.join(PKG, "host")

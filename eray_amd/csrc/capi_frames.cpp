@@ -50,7 +50,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     if (!rp) return set_error(ctx, ERAY_E_INVALID_ARGUMENT, "params is null");
     // anti-aliasing and reflection bounces take the general tracer (trace.hip); bounces only
     // matter when some material has a reflection output (engine.rs:181-182)
-    const uint32_t bounces = scene_reflective(ctx) ? rp->bounces : 0u;
+    const uint32_t bounces = scene_reflective(ctx->objects) ? rp->bounces : 0u;
     const bool general = rp->anti_aliasing > 0 || bounces > 0;
     uint32_t W, H;
     eray_camera_size(&ctx->camera, &W, &H);
@@ -61,7 +61,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     *empty = !rp->rows || !W;
     if (*empty) return ERAY_OK;
     // the general tracer's camera rays scan the binned objects' bins (a setup of its own kind)
-    const bool trace_bins = general && !(rp->flags & ERAY_RENDER_BRUTE_FORCE) && ctx->binned > 0;
+    const bool trace_bins = general && !(rp->flags & ERAY_RENDER_BRUTE_FORCE) && ctx->descs.binned > 0;
     bool known = true;
     if (cull || trace_bins)
         if (int st = sync_setup(ctx, W, H, row_span(rp), wait == SetupWait::kYes, &known, trace_bins)) return st;
@@ -99,8 +99,8 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     p.max_object_tris = max_object_tris(ctx);
     p.total_tris = ctx->total_tris;
     p.lds_scene = (ctx->total_tris <= kCacheTris && p.nobj <= kCacheObjects && p.nlights <= kCacheLights) ? 1u : 0u;
-    p.spec_pow = ctx->spec_pow ? 1u : 0u;
-    p.example_mat = ctx->example_mat ? 1u : 0u;
+    p.spec_pow = ctx->descs.spec_pow ? 1u : 0u;
+    p.example_mat = ctx->descs.example_mat ? 1u : 0u;
     p.tiles_x = frame_tiles_x(W);
     p.bins_x = bin_cols(W);
     p.bin_phase = bin_phase(rp->row0);
@@ -129,7 +129,7 @@ int prepare_render(eray_ctx* ctx, const eray_render_params* rp, FrameParams* out
     }
     // the setup's detail sub-block list (ordered: heavy ones first), the frame kernel's for binned
     // objects or the tracer's (trace.hip trace_binned_kernel, trace_heavy_kernel)
-    if (trace_bins || (cull && ctx->binned)) {
+    if (trace_bins || (cull && ctx->descs.binned)) {
         p.detail_list = ctx->bins.dlist;
         p.detail_heavy = ctx->bins.dcount;
         p.detail_occ = ctx->bins.docc;
@@ -839,7 +839,7 @@ int eray_render_camera_path_ring(eray_ctx* ctx, const eray_render_params* rp, co
     if (!c.p.cull) return general_path(ctx, rp, c.p, c.r, cameras, n, mean_frame_ms);
     if (int st = stage_path_cameras(ctx, cameras, n)) return st;
     if (batch_setup_ok(ctx)) return run_path(BatchedPath(ctx, rp, c.p, c.r, n), mean_frame_ms);
-    if (ctx->binned) return run_path(MultiPath(ctx, rp, c.p, c.r, n), mean_frame_ms);
+    if (ctx->descs.binned) return run_path(MultiPath(ctx, rp, c.p, c.r, n), mean_frame_ms);
     return run_path(PerFramePath(ctx, rp, c.p, c.r, n), mean_frame_ms);
 }
 

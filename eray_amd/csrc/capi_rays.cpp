@@ -58,7 +58,7 @@ int eray_cast_rays(eray_ctx* ctx, const eray_rays_params* rp) {
     p.nobj = (uint32_t)ctx->objects.size();
     p.nlights = (uint32_t)ctx->lights.size();
     p.total_tris = ctx->total_tris;
-    p.bounces = scene_reflective(ctx) ? rp->bounces : 0u;
+    p.bounces = scene_reflective(ctx->objects) ? rp->bounces : 0u;
     b.rays = reinterpret_cast<const RayIn*>(rp->rays);
     b.count = rp->count;
     b.object = rp->object;
@@ -300,7 +300,7 @@ int eray_scene_refit_ray_accel_async(eray_ctx* ctx) {
         return set_error(ctx, ERAY_E_INVALID_ARGUMENT,
                          "%s: the scene's objects are not those of the build (eray_scene_refit_ray_accel rebuilds)", fn);
     // first of all HIP calls, so that a refusal leaves a capture as it was (the null stream never
-    // captures and is not asked: capi.cpp order_after_side_streams)
+    // captures and is not asked: capi_scene.cpp order_after_side_streams)
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     if (ctx->stream) HIP_TRY(ctx, hipStreamIsCapturing(ctx->stream, &capturing));
     if (!ra.refit.ready()) {

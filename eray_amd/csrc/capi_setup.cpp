@@ -34,7 +34,7 @@ uintptr_t tag_end(const eray_ctx::SlotTag& t) { return t.ppm + (uintptr_t)t.src.
 void binned_lists(const eray_ctx* ctx, std::vector<uint32_t>* kbegin, std::vector<uint32_t>* kobj) {
     for (uint32_t i = 0; i < ctx->objects.size(); ++i)
         if (ctx->objects[i].T > kDirectMax) {
-            kbegin->push_back(ctx->h_objs[i].g.tri_begin);
+            kbegin->push_back(ctx->descs.objs[i].g.tri_begin);
             kobj->push_back(i);
         }
 }
@@ -43,7 +43,7 @@ void binned_lists(const eray_ctx* ctx, std::vector<uint32_t>* kbegin, std::vecto
 // (reallocated, with a stream synchronisation, only when that layout or the capacity changes).
 int ensure_bins(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
     const uint32_t row0 = rs.row0, rows = rs.rows;
-    const uint32_t nb = ctx->binned;
+    const uint32_t nb = ctx->descs.binned;
     const uint32_t T = ctx->total_tris;
     int st;
     if ((st = ctx->d_range.ensure(ctx, T)) || (st = ctx->d_area.ensure(ctx, T)) || (st = ctx->d_fkey.ensure(ctx, T)))
@@ -139,12 +139,10 @@ SetupParams setup_params(eray_ctx* ctx, const BinBuffers& bins, const CamDev* d_
     sp.band_shift = rs.band_shift;
     sp.band_mask = rs.band_mask;
     sp.band_stride = rs.band_stride;
-    // [done counter | kSetupMaxBlocks x 10 partials | 4 x nobj accumulators]: the counter and the
-    // accumulators are zero between setups whatever the object count (partials are rewritten)
     sp.done = ctx->d_acc;
-    sp.part = ctx->d_acc + 1;
-    sp.acc = ctx->d_acc + 1 + 10 * (size_t)kSetupMaxBlocks;
-    const bool binned = ctx->binned > 0;
+    sp.part = ctx->d_acc + kSetupAccPart;
+    sp.acc = ctx->d_acc + kSetupAccRects;
+    const bool binned = ctx->descs.binned > 0;
     sp.binned = binned ? 1u : 0u;
     sp.rect_pairs = ctx->rect_pairs ? 1u : 0u;
     if (binned) {
@@ -195,9 +193,9 @@ int ensure_multi(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->mc_stream));
     ctx->mc_layout.clear();
-    const uint32_t T = ctx->total_tris, nobj = (uint32_t)ctx->objects.size(), nb = ctx->binned;
+    const uint32_t T = ctx->total_tris, nobj = (uint32_t)ctx->objects.size(), nb = ctx->descs.binned;
     const size_t t = (size_t)K * (T ? T : 1);
-    const size_t acc_words = 4 * (size_t)K * nobj + 1 + 10 * (size_t)kSetupMaxBlocks;
+    const size_t acc_words = setup_acc_words((size_t)K * nobj);
     // camera k's copy of binned object j: key k * nb + j, its faces from k * T + tri_begin
     std::vector<uint32_t> kbegin, kobj, mbegin, mobj;
     binned_lists(ctx, &kbegin, &kobj);
@@ -236,15 +234,15 @@ int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_ca
     sp.ncam = ncam;
     sp.T1 = T;
     sp.nobj1 = nobj;
-    sp.nb1 = ctx->binned;
+    sp.nb1 = ctx->descs.binned;
     sp.T = ncam * T;
     sp.nobj = ncam * nobj;
     sp.cull = m.cull;
     sp.objs = m.objs;
     sp.state = m.state;
     sp.done = m.acc;
-    sp.part = m.acc + 1;
-    sp.acc = m.acc + 1 + 10 * (size_t)kSetupMaxBlocks;
+    sp.part = m.acc + kSetupAccPart;
+    sp.acc = m.acc + kSetupAccRects;
     sp.range = m.range;
     sp.area = m.area;
     sp.fkey = m.fkey;
@@ -262,7 +260,7 @@ int enqueue_multi_setup(eray_ctx* ctx, eray_ctx::MultiSet& m, const CamDev* d_ca
 // as the frame.  Up to kBatchTris triangles (the slots hold kGraphFrames x T culling records).
 constexpr uint32_t kBatchTris = 16384;
 bool batch_setup_ok(const eray_ctx* ctx) {
-    return !ctx->binned && ctx->objects.size() <= kSetupBatchMaxObjects && ctx->total_tris <= kBatchTris;
+    return !ctx->descs.binned && ctx->objects.size() <= kSetupBatchMaxObjects && ctx->total_tris <= kBatchTris;
 }
 
 CamDev cam_dev(const eray_camera& c) {
@@ -295,7 +293,7 @@ int sync_setup(eray_ctx* ctx, uint32_t W, uint32_t H, const RowSpan& rs, bool wa
             else if (q != hipErrorNotReady) return set_error(ctx, ERAY_E_HIP, "setup event: %s", hipGetErrorString(q));
         }
         auto bins_ready = [&]() -> int {
-            if (!ctx->binned) return ERAY_OK;
+            if (!ctx->descs.binned) return ERAY_OK;
             const std::vector<uint64_t> before = ctx->bins_layout;
             if (int st = ensure_bins(ctx, W, H, rs)) return st;
             if (ctx->bins_layout != before)  // new buffers: the bin statistics start over

@@ -1,9 +1,10 @@
 // ctx.hpp — the context behind include/eray_hip.h's eray_ctx handle and what the C-ABI translation
-// units share to work on it: capi.cpp (context, memory, shaderlib nodes, scene, the eray_debug_*
-// hooks), capi_setup.cpp (camera setup, bins, frame tags), capi_frames.cpp (the frame entry
-// points), capi_rays.cpp (ray queries and their hierarchy) and comm.cpp (the multi-GPU gather).
+// units share to work on it: capi.cpp (context, memory, shaderlib nodes), capi_scene.cpp (the scene
+// calls and the scene's upload), capi_debug.cpp (the eray_debug_* hooks of the bins and the setup),
+// capi_setup.cpp (camera setup, bins, frame tags), capi_frames.cpp (the frame entry points),
+// capi_rays.cpp (ray queries and their hierarchy) and comm.cpp (the multi-GPU gather).
 // Here: the error policy (set_error, HIP_TRY, use_device), the scene upload, and what the other
-// units need of capi_setup.cpp — declared here and nowhere else.  Private to those five files; the
+// units need of capi_setup.cpp — declared here and nowhere else.  Private to those seven files; the
 // HIP-free units report errors without it (objload.cpp through capi.cpp's eray_internal_error).
 #pragma once
 
@@ -26,22 +27,7 @@ namespace gpu {
 
 constexpr uint32_t kUnionRing = 4;  // camera paths whose rectangle unions the host keeps
 
-struct HostObject {
-    std::vector<float> raw;  // T*9 positions | T*9 normals | T*6 uvs
-    uint32_t T = 0;
-    // eray_scene_update_object replaced (part of) the geometry from device arrays: the resident raw
-    // array holds it, `raw` does not (refresh_raw reads it back before the scene is uploaded again)
-    bool raw_stale = false;
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    eray_material mat{};
-    bool example = false;  // color + diffuse from main.rs's graph at the hit texel
-    eray_material_example_params ex{};
-    std::vector<eray_texel_node> tnodes;  // a shader graph per hit texel (texel_graph)
-    int32_t tout[5] = {-1, -1, -1, -1, -1};
-};
-
-// Node types of the shaderlib outputs: wave's is IValue, rgb / flat_color / mix_color's IColor.
-inline bool texel_is_color(uint32_t kind) { return kind != ERAY_TEXEL_WAVE; }
+// (HostObject, an object of the host scene: scene_build.hpp.)
 
 // eray_gather_frames' plan: comm.cpp defines it, and how it is deleted.
 struct GatherPlan;
@@ -80,14 +66,9 @@ struct eray_ctx {
     uint64_t graph_clock = 0;
     DeviceBuf<uint32_t> d_prog;  // every object's texel program (MaterialDesc::prog), concatenated
     std::vector<uint32_t> h_prog;
-    std::vector<ObjectDesc> h_objs;  // kept alive for the async uploads
-    std::vector<LightDesc> h_lights;
+    SceneDescs descs;  // the descriptors as uploaded (scene_build.hpp; kept alive for the async uploads)
     std::vector<float> h_raw;
-    std::vector<uint32_t> h_begin;   // obj_begin (nobj + 1) | objkey (nobj), uploaded with the descriptors
     uint32_t total_tris = 0;
-    uint32_t binned = 0;       // objects of more than kDirectMax faces (sync_scene)
-    bool spec_pow = false;     // some material has a specular-power output
-    bool example_mat = false;  // some material is main.rs's graph evaluated per hit
     // ---- per-camera setup (setup.hip, bins.hip), all on the device
     DeviceBuf<CamDev> d_cam;      // the context camera's device slot
     DeviceBuf<CamState> d_state;  // the last setup's results
@@ -191,17 +172,6 @@ struct eray_ctx {
 namespace eray {
 namespace gpu {
 
-// Does some material reflect?  Bounces only matter then (engine.rs:181-182).  A graph output
-// replaces the texture (None if mistyped).
-inline bool scene_reflective(const eray_ctx* ctx) {
-    bool reflective = false;
-    for (auto& o : ctx->objects) {
-        const int32_t r = o.tout[4];
-        reflective |= r >= 0 ? !texel_is_color(o.tnodes[r].kind) : o.mat.reflection.data != nullptr;
-    }
-    return reflective;
-}
-
 // The ray-query hierarchy as the kernels take it: none unless it is valid (never a stale tree: every
 // geometry change clears `valid`).
 inline RayAccelView accel_view(const eray_ctx* ctx) {
@@ -228,7 +198,7 @@ inline int use_device(eray_ctx* ctx) {
     return ERAY_OK;
 }
 
-// Uploads what changed of the scene (geometry, descriptors) on the context's stream (capi.cpp).
+// Uploads what changed of the scene (geometry, descriptors) on the context's stream (capi_scene.cpp).
 int sync_scene(eray_ctx* ctx);
 
 // ---- the frame path's per-camera state (capi_setup.cpp) ----

@@ -4,15 +4,33 @@
 // hipcc's default correctly rounded f32 division and sqrt and f32 denormals preserved, so
 // each helper below performs the same IEEE operations, in the same order, as the Rust
 // source it cites.  That is what makes GPU results bit-identical to the reference semantics.
+//
+// sat_u32 is also the host's (eray_camera_size, the texel programs' CPU checker): without a HIP
+// compiler the header holds that function alone and includes no HIP header.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define ERAY_HD_FORCEINLINE __host__ __device__ __forceinline__  // (a name of its own: ERAY_HD differs by header)
+#else
+#define ERAY_HD_FORCEINLINE inline
+#endif
 
 #include "glibc_powf.hpp"
 
 namespace eray {
 namespace dev {
+
+// `x as u32`: saturating, NaN -> 0, truncation toward zero.
+ERAY_HD_FORCEINLINE uint32_t sat_u32(float f) {
+    if (!(f > 0.0f)) return 0u;
+    if (f >= 4294967296.0f) return 0xffffffffu;
+    return (uint32_t)f;
+}
+
+#if defined(__HIPCC__) || defined(__HIP__)
 
 struct f3 {
     float x, y, z;
@@ -63,12 +81,7 @@ __device__ __forceinline__ float rust_clamp(float x, float lo, float hi) {
     if (x > hi) x = hi;
     return x;
 }
-// `x as u32` / `x as u8`: saturating, NaN -> 0, truncation toward zero.
-__device__ __forceinline__ uint32_t sat_u32(float f) {
-    if (!(f > 0.0f)) return 0u;
-    if (f >= 4294967296.0f) return 0xffffffffu;
-    return (uint32_t)f;
-}
+// `x as u8`: as sat_u32 (above).
 __device__ __forceinline__ uint32_t sat_u8(float f) {
     if (!(f > 0.0f)) return 0u;
     if (f >= 255.0f) return 255u;
@@ -83,6 +96,8 @@ __device__ __forceinline__ float powf_ref(float x, float y) {
     if (y == 1.0f) return x;
     return libm::powf_glibc(x, y);
 }
+
+#endif  // HIP compile
 
 }  // namespace dev
 }  // namespace eray

@@ -1,4 +1,7 @@
-// internal.hpp — descriptors shared by the C-ABI layer (capi*.cpp) and the gfx950 kernels.
+// internal.hpp — records, constants and launchers shared by the C-ABI layer (capi*.cpp) and the
+// gfx950 kernels.  What the host decides without the GPU lives in HIP-free headers included here:
+// the descriptors and their build (scene_build.hpp), the texel programs (texel_prog.hpp), the
+// frame launch's arguments (frame_params.hpp), the bins' sizing (bin_layout.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -6,6 +9,11 @@
 
 #include <array>
 #include <vector>
+
+// (these two before accel_walk.hpp: they bring in glibc_cosf.hpp, whose ERAY_HD is for its own
+// functions; the headers after this one that use ERAY_HD mean accel_walk.hpp's, as before)
+#include "scene_build.hpp"
+#include "texel_prog.hpp"
 
 #include "accel_walk.hpp"
 #include "band_rows.hpp"
@@ -41,41 +49,8 @@ struct __align__(16) TriCull {
     float4 T;  // thresholds (>= 0; +inf disables the condition)
 };
 
-struct TexView {
-    const float* data;  // nullptr: the output is absent (Option::None)
-    uint32_t w, h;
-};
-
-// One node of a material output's expression tree, evaluated per hit texel (hit.hpp
-// texel_program): the host expands the shader graph (eray_texel_graph) per output into a tree in
-// pre-order — a node shared along different paths is evaluated at each path's texel — where
-// every node's texel derives from its parent's.
-struct TexelInstr {  // 48 B
-    uint32_t kind;    // eray_texel_node_kind
-    uint32_t w, h;    // the node's image size
-    uint32_t parent;  // instruction index of the parent (0: the root itself)
-    uint32_t xform;   // kTexelMod: parent texel mod (w, h) (mix's mod_get); kTexelIndex: the
-                      // parent's pixel index y * w_parent + x as (i % w, i / w) (rgb's pixels[i])
-    float p[3];
-    uint32_t c[3];    // children (later instructions; rgb's identical inputs share one)
-    uint32_t pad;
-};
-constexpr uint32_t kTexelMod = 0, kTexelIndex = 1;
-constexpr uint32_t kTexelMaxNodes = 32;  // per output tree
-// Program header (uint32 words): first instruction and count per Material output (color,
-// diffuse, specular, specular_power, reflection), count 0 = not a program output; then the
-// instructions from word kTexelHeaderWords (48-B records).
-constexpr uint32_t kTexelHeaderWords = 12;
-
-struct MaterialDesc {
-    TexView color;  // IColor, 3 floats per texel
-    TexView diffuse, specular, specular_power, reflection;  // IValue
-    // example: 1 = color and diffuse are main.rs's graph evaluated at the hit texel
-    uint32_t example, ex_w, ex_h;
-    float ex_xf, ex_yf, ex_r, ex_g, ex_b, ex_factor;
-    // a shader graph per hit texel (eray_scene_set_object_texel_graph), or null
-    const uint32_t* prog;
-};
+// (TexelInstr and the texel programs' constants: texel_prog.hpp.  TexView, MaterialDesc, ObjGeom,
+// ObjectDesc and LightDesc, the descriptors the host builds: scene_build.hpp.)
 
 // Scenes up to these sizes are preloaded whole into each frame workgroup's LDS.
 constexpr uint32_t kCacheTris = 256, kCacheObjects = 16, kCacheLights = 16;
@@ -110,31 +85,6 @@ struct alignas(16) BinEntry {
     uint32_t pad;  // sorted bins: half of the later chunks' mask union (kBinSortMax), else 0
 };
 static_assert(sizeof(BinEntry) == 64, "one 64-B line per bin entry");
-
-struct ObjGeom {  // what the triangle scans need of an object, 64 B
-    uint32_t tri_begin, tri_count;
-    // Camera pixels whose primary ray can hit the object: x0..x1 x y0..y1 (inclusive, camera
-    // rows), from the culling records (tri_rect_kernel); empty when x0 > x1.
-    int32_t rect[4];
-    float bb_lo[3], bb_hi[3];
-    // Screen bins of a large object's faces (bins.hip), or null: bin b's entries are
-    // bin_ent[bin_start[b] .. bin_start[b + 1]) (bins of 65..kBinSortMax entries in increasing
-    // face index, with the later chunks' mask unions, BinEntry).
-    const uint32_t* bin_start;
-    const BinEntry* bin_ent;
-};
-
-struct alignas(16) ObjectDesc {  // 192 B: the LDS scene copy moves whole 16-B words
-    ObjGeom g;
-    MaterialDesc mat;
-};
-
-struct LightDesc {
-    float pos[3];
-    int32_t variant;  // 0 point, 1 ambient
-    float color[3];
-    float brightness;
-};
 
 // A camera as the kernels use it (camera.rs:57-76): centre, Fov ratio fov0 / fov1 (computed on
 // the host in f32, as Fov::ratio does) and z_dist.  Camera::size is fixed per frame plan.
@@ -179,7 +129,7 @@ __host__ __device__ inline SceneLdsLayout scene_lds_layout(uint32_t nobj, uint32
     L.bytes = L.shade + n * (uint32_t)sizeof(TriShade);
     return L;
 }
-static_assert(sizeof(ObjectDesc) % 16 == 0 && sizeof(LightDesc) % 16 == 0, "16-B words");
+// (whole 16-B words: scene_build.hpp asserts ObjectDesc's and LightDesc's sizes)
 
 // ------------------------------------------------------------- launchers (.hip files) ------
 hipError_t launch_tri_precompute(const float* pos, const float* nrm, const float* uv, uint32_t T,
@@ -207,6 +157,11 @@ inline uint32_t setup_blocks(uint32_t T) {
     const uint32_t b = (T + 255u) / 256u;
     return T ? (b < kSetupMaxBlocks ? b : kSetupMaxBlocks) : 1u;
 }
+// The setup's accumulator words (SetupParams::done / part / acc point into one array): [done
+// counter | kSetupMaxBlocks x 10 partials | 4 x nobj rectangle accumulators].  The counter and the
+// accumulators are zero between setups whatever the object count (partials are rewritten).
+constexpr size_t kSetupAccPart = 1, kSetupAccRects = kSetupAccPart + 10 * (size_t)kSetupMaxBlocks;
+inline size_t setup_acc_words(size_t nobj) { return kSetupAccRects + 4 * nobj; }
 struct SetupParams {
     const TriHot* hot;
     TriCull* cull;

@@ -1,6 +1,6 @@
 // rays_args.hpp — eray_cast_rays', eray_rays_reach_light's and eray_scene_update_object's argument
 // validation (include/eray_hip.h states the rules): plain host code with no HIP call, so the C-ABI
-// layer (capi_rays.cpp; the update: capi.cpp) and the stand-alone checkers (tests/cpp/rays_args_main.cpp, tests/cpp/reach_args_main.cpp,
+// layer (capi_rays.cpp; the update: capi_scene.cpp) and the stand-alone checkers (tests/cpp/rays_args_main.cpp, tests/cpp/reach_args_main.cpp,
 // tests/cpp/update_args_main.cpp, built with the host sanitizers) share it.
 #pragma once
 

@@ -1,5 +1,5 @@
 // Stand-alone checker of eray_scene_update_object's argument validation (check_update_params in
-// eray_amd/csrc/rays_args.hpp, the function capi.cpp calls): plain host code, no library to link,
+// eray_amd/csrc/rays_args.hpp, the function capi_scene.cpp calls): plain host code, no library to link,
 // meant for the host sanitizers and a machine without a GPU:
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
